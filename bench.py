@@ -3,14 +3,20 @@
 4096 envs per MI355X, joint-space obs). One "step" = one control step of all envs of this rank
 (IK + 20 physics substeps + obs/reward/termination + auto-reset), one kernel launch.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
       N > 1: either launched by torch.distributed.run (RANK / LOCAL_RANK / WORLD_SIZE in the environment), or run
       plainly, in which case this process spawns the N rank processes itself and never touches the GPU.
 
-Prints ONE JSON line on rank 0 (contract in the task statement), including
-  roofline     : algorithmic HBM bytes per launch / HIP-event kernel time vs 8 TB/s
-  cpu_baseline : the CPU oracle (oracle/, a scalar C restatement; kind "port") timed on this
-                 box's host cores on a bounded sample of the same workload (rank 0, N=1 only)
+A plain run sets up, warms up, times the K steps and prints ONE JSON line on rank 0 (metric, value, unit, ms_per_step, ...).
+  --dump-outputs DIR : after the timed steps, write what the LAST timed step returned (the output buffers of
+                       HipVectorEnv.step_flat, and the camera images with --visual) as DIR/<name>.npy, float32 / float64,
+                       at most 64 MB in all; inputs are seeded, so two builds can be compared array for array
+  --full             : everything else, each with runs of its own after the timed region; the line then also carries
+      roofline           : algorithmic HBM bytes per launch / HIP-event kernel time vs 8 TB/s
+      rollout_gather     : N > 1: the all-gather of a rollout block, timed on its own
+      cpu_baseline       : the CPU oracle (oracle/, a scalar C restatement; kind "port") timed on this
+                           box's host cores on a bounded sample of the same workload (rank 0, N=1 only)
+      config1_single_env : BASELINE config 1's single-env loop (Robot-Reach runs, N=1 only)
 """
 from __future__ import annotations
 
@@ -58,7 +64,12 @@ def parse():
     ap.add_argument("--block-shape", default="mesh", choices=["mesh", "box"], help="Planar-Push blocks: the reference's meshes (default) or round 1's box stand-in")
     ap.add_argument("--gripper-model", default="reduced", choices=["reduced", "articulated"],
                     help="Button-Push: the one-coordinate 2F-85 of DESIGN.md D-1b (BASELINE config 5's kernel) or the articulated 2F-85 (SURVEY 8 f-1, nv = 14)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need, after the timed steps: HIP-event kernel time and the roofline block, "
+                         "the rollout gather (N > 1), the CPU oracle baseline and the single-env figures (N = 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle baseline and the single-env figures")
     ap.add_argument("--variant", type=int, default=0, help="kernel variant for A/B profiling (0 = default)")
     ap.add_argument("--visual", type=int, default=0, metavar="RES",
                     help="also render the task's camera(s) at RESxRES every step (BASELINE config 5: Button-Push, 64)")
@@ -225,6 +236,27 @@ class _StubVectorEnv:
         pass
 
 
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(directory, arrays, rank=0):
+    """Write `arrays` (name -> tensor with the env axis first) as <directory>/<name>.npy: float64 stays, everything else becomes
+    float32 (exact for the uint8 / int32 fields). Above DUMP_BUDGET_BYTES in all, every array keeps the same fixed, seeded sample
+    of envs, whose indices go into env_index.npy. Ranks above 0 write <name>_rank<r>.npy."""
+    out = {k: v.detach().cpu().numpy() for k, v in arrays.items()}
+    out = {k: np.ascontiguousarray(v if v.dtype == np.float64 else v.astype(np.float32)) for k, v in out.items()}
+    n = next(iter(out.values())).shape[0]
+    per_env = sum(v.nbytes // max(n, 1) for v in out.values()) + 8
+    if per_env * n > DUMP_BUDGET_BYTES:
+        idx = np.sort(np.random.RandomState(2025).choice(n, max(1, DUMP_BUDGET_BYTES // per_env), replace=False))
+        out = {k: np.ascontiguousarray(v[idx]) for k, v in out.items()}
+        out["env_index"] = idx.astype(np.float64)
+    d = Path(directory)
+    d.mkdir(parents=True, exist_ok=True)
+    for k, v in out.items():
+        np.save(d / (f"{k}.npy" if rank == 0 else f"{k}_rank{rank}.npy"), v)
+
+
 def launch_ranks(args) -> int:
     """``python bench.py --gpus N`` outside torchrun: fan out to N fresh rank processes (the counterpart of the
     reference's ``SubprocVecEnv([create_env(rank=i, seed=...) ...])``, scripts/sb3/reach_sac.py:93-96, one env shard per
@@ -344,13 +376,19 @@ def main():
     D.barrier()
     elapsed = time.perf_counter() - t0
     elapsed = D.max_over_ranks(elapsed, device=device)
+    if args.dump_outputs:  # what the last timed step returned: step_flat's buffers (+ the images), before anything steps again
+        last = dict(venv._buf)
+        for cam, img in zip(cams, imgs):
+            last[f"image_camera{cam}"] = img
+        dump_outputs(args.dump_outputs, last, rank)
 
-    # per-launch kernel time with HIP events on the launch stream (torch's current stream). Each event pair brackets a
-    # short train of back-to-back launches so that the ~4 us cost of the event records themselves is amortised and the
+    # --full: per-launch kernel time with HIP events on the launch stream (torch's current stream). Each event pair brackets
+    # a short train of back-to-back launches so that the ~4 us cost of the event records themselves is amortised and the
     # figure is the kernel's own duration (it then agrees with rocprofv3's per-kernel average, profiles/).
-    if args.stub:
+    kernel_ms = None
+    if args.full and args.stub:
         kernel_ms = elapsed / args.steps * 1e3
-    else:
+    elif args.full:
         train = 10 if not cams else 1
         n_ev = min(40, max(4, args.steps // train))
         evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n_ev)]
@@ -363,11 +401,11 @@ def main():
         kernel_ms = float(np.mean([a.elapsed_time(b) for a, b in evs])) / train
     faults = int(venv._buf["fault"].max().item())
 
-    # N > 1: the one collective of the design — all-gather of a rollout block once per 64-step chunk (RCCL over xGMI;
+    # --full, N > 1: the one collective of the design — all-gather of a rollout block once per 64-step chunk (RCCL over xGMI;
     # gloo in the stub) — outside the timed step region and reported on its own; every rank checks that its own shard
     # came back bit-identical at its global position.
     gather = None
-    if world > 1:
+    if world > 1 and args.full:
         block = venv.rollout(acts, keep=("obs",))["obs"]  # [64, n_local, obs_dim]
         full = D.gather_rollout(block)
         ok = tuple(full.shape) == (chunk, n_global, block.shape[2]) and bool(torch.equal(full[:, rank * n_local:(rank + 1) * n_local], block))
@@ -392,7 +430,6 @@ def main():
         value = env_steps / elapsed
         bytes_per_env_step = venv.algorithmic_bytes_per_env_step
         bytes_per_launch = bytes_per_env_step * n_local
-        achieved = bytes_per_launch / (kernel_ms * 1e-3) / 1e9
         line = {
             "metric": {"robot_reach": "env-steps/sec at N_envs=4096, Robot-Reach", "point_mass_reach": "env-steps/sec, Pointmass-Reach",
                        "robot_push_button": "env-steps/sec, Button-Push (" + (f"scene + wrist camera {args.visual}x{args.visual}" if cams else "state obs") + ")",
@@ -407,17 +444,20 @@ def main():
                        "envs_per_gpu": n_local, "envs_total": n_global, "parallelism": f"env-sharded x{world}, no collective in the step",
                        "scaling_mode": ("weak: envs_per_gpu fixed, envs_total grows with the GPU count" if args.scaling == "weak" else
                                         "strong: envs_total fixed, envs_per_gpu = envs_total / n_gpus (a launch is latency-bound below ~16k envs per GPU: expect ~1x)")},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                         "traffic": None if (args.stub or (args.task == "robot_planar_push" and args.n_objects != 2)) else measured_traffic(args.task + ("_articulated" if (args.task == "robot_push_button" and args.gripper_model == "articulated") else ""), n_local), "kernel_ms": kernel_ms, "algorithmic_bytes_per_env_step": bytes_per_env_step,
-                         "note": "state fits in L2 at this size; the kernel is bound by per-lane FP64 dependency chains (DESIGN.md)"},
             "faults": faults,
         }
+        if args.full:
+            achieved = bytes_per_launch / (kernel_ms * 1e-3) / 1e9
+            line["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+                                "traffic": None if (args.stub or (args.task == "robot_planar_push" and args.n_objects != 2)) else measured_traffic(args.task + ("_articulated" if (args.task == "robot_push_button" and args.gripper_model == "articulated") else ""), n_local), "kernel_ms": kernel_ms, "algorithmic_bytes_per_env_step": bytes_per_env_step,
+                                "note": "state fits in L2 at this size; the kernel is bound by per-lane FP64 dependency chains (DESIGN.md)"}
+            line["faults"] = line.pop("faults")  # key order of the line as before
         if args.stub:
             line["stub"] = True
             line["data"] = "STUB: launcher self-test on CPU, no physics, not a measurement"
         if gather is not None:
             line["rollout_gather"] = gather
-        if args.task == "robot_reach" and not args.stub:
+        if args.full and args.task == "robot_reach" and not args.stub:
             # informational: the bound that actually applies. FP64 operation count per env-step:
             # 20 substeps x (generated M + bias code 725 ops + servo/actuators/U D U^T/inverse/integration ~330) + IK ~3000
             # + FK/observables ~500; peak = 1024 SIMDs x 16 FP64 FMA lanes x 2 x ~2.4 GHz (public spec 78.6 TFLOP/s;
@@ -432,7 +472,7 @@ def main():
                     line["roofline"]["valu_fp64"]["valu_busy_frac_on_occupied_simds_pmc"] = v["valu_busy_frac_of_wave_lifetime"]
             except Exception:  # noqa: BLE001
                 pass
-        if world == 1 and not args.no_cpu_baseline and not args.stub:
+        if args.full and world == 1 and not args.no_cpu_baseline and not args.stub:
             line["cpu_baseline"] = cpu_baseline(args.task, n_local, args.cpu_seconds, args.n_objects, args.block_shape, args.gripper_model)
             line["cpu_baseline"].update(mujoco_probe())  # "mujoco_on_box": asked on every run, acted on only when true
             if args.task == "robot_reach":

@@ -2406,3 +2406,38 @@ def test_robot_helper_surface(oracle_mod):
     assert rob.is_moving().all()
     with pytest.raises(NotImplementedError):
         rob.moveL(pose, 0.1)
+
+
+def test_bench_dump_outputs_holds_the_last_timed_step(oracle_mod, tmp_path):
+    """`bench.py --dump-outputs DIR` writes what the timed path returned in its LAST timed step, and a plain run carries no
+    figure that needs runs of its own. Robot-Reach, 96 envs (two workgroups, the second half full), 2 warm-up + 3 timed steps of
+    bench.py's seeded actions (slab i % 64 of RandomState(12345), the timed loop starting at slab 0 again): the oracle under the
+    same seeds and actions gives the expected arrays, to this file's tolerance; flags exact."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    root = Path(__file__).resolve().parents[1]
+    N, W, K = 96, 2, 3
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    res = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "1", "--steps", str(K), "--warmup", str(W), "--envs-per-gpu", str(N),
+                          "--dump-outputs", str(tmp_path / "out")], capture_output=True, text=True, timeout=300, env=env)
+    assert res.returncode == 0, res.stderr[-3000:]
+    lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, res.stdout[-2000:]
+    line = json.loads(lines[0])
+    assert line["steps"] == K and line["warmup"] == W and line["faults"] == 0 and line["config"]["envs_per_gpu"] == N
+    assert abs(line["value"] - N / (line["ms_per_step"] * 1e-3)) < 1e-6 * line["value"]
+    assert not {"roofline", "rollout_gather", "cpu_baseline", "config1_single_env"} & set(line)
+    got = {p.stem: np.load(p) for p in (tmp_path / "out").iterdir()}
+    assert sorted(got) == sorted(("obs", "terminal_obs", "reward", "discount", "ncon", "terminated", "truncated", "is_success", "step_type", "fault"))
+    for k, v in got.items():
+        assert v.dtype == (np.float64 if k in ("obs", "terminal_obs", "reward", "discount") else np.float32) and v.shape[0] == N, k
+    acts = _actions("robot_reach", 64, N)
+    ob = oracle_mod.OracleBatch(oracle_mod.TASK_ROBOT_REACH, N, 2025, nthreads=8)
+    ob.reset()
+    for i in [*range(W), *range(K)]:
+        o = ob.step(acts[i % 64])
+    _compare(K - 1, got, o)
+    assert not got["fault"].any() and not o["fault"].any()

@@ -147,7 +147,7 @@ def test_bench_gpus2_launches_its_own_ranks():
     import sys
 
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
-    res = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--stub", "--steps", "5", "--warmup", "1"],
+    res = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--stub", "--steps", "5", "--warmup", "1", "--full"],
                          capture_output=True, text=True, timeout=300, env=env)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
@@ -177,7 +177,7 @@ def test_bench_strong_scaling_mode_splits_a_fixed_env_count():
     import time
 
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
-    res = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--stub", "--steps", "4", "--warmup", "1", "--scaling", "strong"],
+    res = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--stub", "--steps", "4", "--warmup", "1", "--scaling", "strong", "--full"],
                          capture_output=True, text=True, timeout=300, env=env)
     assert res.returncode == 0, res.stderr[-2000:]
     line = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][-1])
@@ -191,6 +191,48 @@ def test_bench_strong_scaling_mode_splits_a_fixed_env_count():
     res = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--stub", "--steps", "1", "--warmup", "0", "--scaling", "strong",
                           "--envs-per-gpu", "4097"], capture_output=True, text=True, timeout=300, env=env)
     assert res.returncode != 0 and "divisible" in res.stderr and time.time() - t0 < 120
+
+
+def test_bench_plain_run_is_lean_and_dumps_its_last_step(tmp_path):
+    """A plain `bench.py` run carries the headline figures only (what takes runs of its own sits behind --full), and
+    --dump-outputs DIR writes what the last timed step returned as float32 / float64 .npy files. Stub env, one process: its
+    obs[:, 0] counts the calls of step_flat, so the dump must hold warmup + steps there and nothing stepped it afterwards."""
+    import json
+    import subprocess
+    import sys
+
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    res = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--stub", "--steps", "3", "--warmup", "1", "--envs-per-gpu", "8",
+                          "--dump-outputs", str(tmp_path / "out")], capture_output=True, text=True, timeout=300, env=env)
+    assert res.returncode == 0, res.stderr[-2000:]
+    lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, res.stdout
+    line = json.loads(lines[0])
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["unit"] == "env-steps/s" and line["higher_is_better"] is True and line["dtype"] == "f64"
+    assert abs(line["value"] - 3 * 8 / (line["ms_per_step"] * 3 * 1e-3)) < 1e-6 * line["value"]
+    assert not {"roofline", "rollout_gather", "cpu_baseline", "config1_single_env"} & set(line)
+    assert sorted(p.name for p in (tmp_path / "out").iterdir()) == ["fault.npy", "obs.npy"]
+    obs, fault = np.load(tmp_path / "out" / "obs.npy"), np.load(tmp_path / "out" / "fault.npy")
+    assert obs.dtype == np.float64 and obs.shape == (8, 12) and fault.dtype == np.float32 and fault.shape == (8,)
+    assert np.array_equal(obs[:, 0], np.full(8, 4.0)) and not obs[:, 1:].any() and not fault.any()
+
+
+def test_bench_dump_samples_a_large_output_within_its_budget(tmp_path):
+    """Above 64 MB in all, the dump keeps one fixed, seeded sample of envs, the same rows of every array, and says which."""
+    import bench
+
+    n = 3000
+    big = torch.arange(n, dtype=torch.float64)[:, None].expand(n, 4096).contiguous()  # 98 MB
+    small = torch.arange(n, dtype=torch.int32)
+    for d in ("a", "b"):
+        bench.dump_outputs(tmp_path / d, {"big": big, "small": small})
+    a = {p.stem: np.load(p) for p in (tmp_path / "a").iterdir()}
+    assert sorted(a) == ["big", "env_index", "small"]
+    assert sum(v.nbytes for v in a.values()) <= 64 * 1000 * 1000 and len(a["env_index"]) > n // 2
+    assert a["big"].dtype == np.float64 and a["small"].dtype == np.float32
+    assert np.array_equal(a["big"][:, 0], a["env_index"]) and np.array_equal(a["small"], a["env_index"]) and np.all(np.diff(a["env_index"]) > 0)
+    for k, v in a.items():
+        assert np.array_equal(v, np.load(tmp_path / "b" / f"{k}.npy"))
 
 
 def test_lerobot_recorder_schema_and_round_trip(tmp_path):

@@ -12,7 +12,7 @@ mkdir -p $out
 export TMPDIR=/tmp
 stats() {  # name, bench args...
   local name=$1; shift
-  rocprofv3 --kernel-trace --stats -d $out/kt_$name -o $name --output-format csv -- python3 bench.py "$@" > $out/kt_$name.json 2> $out/kt_$name.log || echo "kernel-trace $name failed"
+  rocprofv3 --kernel-trace --stats -d $out/kt_$name -o $name --output-format csv -- python3 bench.py --full "$@" > $out/kt_$name.json 2> $out/kt_$name.log || echo "kernel-trace $name failed"
 }
 pmc() {  # name, counters (quoted), bench args...
   local name=$1 counters=$2; shift 2
