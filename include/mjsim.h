@@ -24,7 +24,9 @@ extern "C" {
 
 /* 2 (round 3): mjs_config starts with struct_size (validated by mjs_create: a caller built against another header is refused
  * instead of being read past its end); Robot-Reach / Button-Push state blocks grew 18 rows (qacc_warmstart, carried cos / sin):
- * checkpoints of abi 1 do not fit mjs_set_state any more (mjs_state_dim reports the new widths). */
+ * checkpoints of abi 1 do not fit mjs_set_state any more (mjs_state_dim reports the new widths).
+ * 3 (round 4): mjs_config ends with gripper_model and reserved0 (80 bytes; a 72-byte abi 2 config is refused by the struct_size
+ * check). Entry points added since (mjs_env_algorithmic_bytes_per_env_step) leave mjs_config, and so the number, alone. */
 #define MJS_ABI_VERSION 3
 
 /* tasks (environments/tasks/*.py) */
@@ -36,8 +38,9 @@ enum {
 };
 /* Button-Push action spaces (robot_push_button.py:35-36,143-157): absolute joints + gripper (7-D, the
  * registered default) or absolute TCP position + gripper (4-D). The last component is the commanded finger opening in
- * metres, [0, 0.085] (Robotiq2f85.move, gripper.py:77-84): it drives the reduced 2F-85 of this build (driver angle and
- * velocity = rows 16, 17 of the Button-Push state). Other tasks ignore the field. */
+ * metres, [0, 0.085] (Robotiq2f85.move, gripper.py:77-84): it drives the handle's 2F-85, either the reduced one (the default;
+ * driver angle and velocity = rows 16, 17 of the Button-Push state) or the articulated one
+ * (mjs_config.gripper_model). Other tasks ignore the field. */
 enum { MJS_ACTION_ABS_JOINT = 0, MJS_ACTION_ABS_EEF = 1 };
 /* reward types: point_reach.py:11-14, robot_reach.py:37-38 */
 enum { MJS_REW_SPARSE = 0, MJS_REW_DENSE_POTENTIAL = 1, MJS_REW_DENSE_NEG_DISTANCE = 2, MJS_REW_DENSE_BIASED_NEG_DISTANCE = 3 };
@@ -154,12 +157,17 @@ int mjs_action_dim_for(int task, int action_type);
  * keeps rows that belong to the given q (a checkpoint resumes bit for bit) and rewrites them with exact values otherwise (a
  * caller that edits q need not touch them); it also recomputes the flags that are functions of the configuration. */
 int mjs_state_dim(int task);
-/* the same two widths for a created handle: Planar-Push with n_objects 3..5 uses 5 block slots
- * (obs 5 + 2*5 = 15, state 1 + 17 + 13*5 = 83); the per-task queries above describe the 2-slot layout */
+/* the same two widths for a created handle. The per-task queries above describe each task's default instance: Planar-Push with
+ * 2 block slots (obs 5 + 2*2 = 9; state 114 = two worlds of 17 + 15*2 = 47 rows, the current one and the prepared next episode,
+ * + its progress row + the servo set-point 6 + cos / sin 12 + the flag row), Button-Push with the reduced gripper. Planar-Push
+ * with n_objects 3..5 uses 5 block slots (obs 5 + 2*5 = 15, state 2 * (17 + 15*5) + 1 + 6 + 12 + 1 = 204), Button-Push with
+ * MJS_GRIPPER_ARTICULATED 61 rows. */
 int mjs_env_obs_dim(const mjs_handle* h);
 int mjs_env_state_dim(const mjs_handle* h);
-/* algorithmic HBM bytes one env-step moves (state R+W, action, outputs), from the real layout */
+/* algorithmic HBM bytes one env-step moves (state R+W, action, outputs), from the real layout: of the task's default instance,
+ * and of the instance a created handle runs (what a roofline figure for that handle uses) */
 int mjs_algorithmic_bytes_per_env_step(int task);
+int mjs_env_algorithmic_bytes_per_env_step(const mjs_handle* h);
 /* physics substeps per control step: 5 (point_reach.py:24-25) / 20 (robot_reach.py:62-63, robot_planar_push.py:51-52,
  * robot_push_button.py:38-39) */
 int mjs_substeps(int task);

@@ -37,7 +37,7 @@ UR_CMD_NONE, UR_CMD_MOVEJ, UR_CMD_MOVEJ_IK, UR_CMD_SERVOL, UR_CMD_SERVOJ = 0, 1,
 UR_EEF_NONE, UR_EEF_GRIPPER = 0, 1
 
 EXPORTED_SYMBOLS = [
-    "mjs_version", "mjs_obs_dim", "mjs_action_dim", "mjs_action_dim_for", "mjs_state_dim", "mjs_env_obs_dim", "mjs_env_state_dim", "mjs_algorithmic_bytes_per_env_step", "mjs_substeps",
+    "mjs_version", "mjs_obs_dim", "mjs_action_dim", "mjs_action_dim_for", "mjs_state_dim", "mjs_env_obs_dim", "mjs_env_state_dim", "mjs_algorithmic_bytes_per_env_step", "mjs_env_algorithmic_bytes_per_env_step", "mjs_substeps",
     "mjs_create", "mjs_destroy", "mjs_last_error", "mjs_seed", "mjs_reset", "mjs_step", "mjs_rollout",
     "mjs_get_state", "mjs_set_state", "mjs_get_rng_state", "mjs_set_rng_state", "mjs_render", "mjs_debug_ur5e_ik", "mjs_ur5e_tcp_to_joints", "mjs_ur5e_robot_run",
 ]
@@ -148,7 +148,7 @@ def lib() -> C.CDLL:
     for name in ("mjs_obs_dim", "mjs_action_dim", "mjs_state_dim", "mjs_algorithmic_bytes_per_env_step", "mjs_substeps"):
         getattr(L, name).argtypes = [C.c_int]
         getattr(L, name).restype = C.c_int
-    for name in ("mjs_env_obs_dim", "mjs_env_state_dim"):
+    for name in ("mjs_env_obs_dim", "mjs_env_state_dim", "mjs_env_algorithmic_bytes_per_env_step"):
         getattr(L, name).argtypes = [C.c_void_p]
         getattr(L, name).restype = C.c_int
     L.mjs_action_dim_for.argtypes = [C.c_int, C.c_int]

@@ -2,8 +2,8 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
-#include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <string>
 
@@ -15,25 +15,98 @@
 #include "mjs_gripper14.h"
 #include "mjs_push.h"
 #include "mjs_render.h"
+#ifdef MJS_STAMPS
+#include "mjs_stamps_report.h"
+#endif
 #include <cmath>
+
+// The six kernel instances. A handle runs one of them, resolved once in mjs_create (resolve_instance); the first four are the
+// tasks' default instances, numbered like the tasks.
+enum Kind { KIND_POINTMASS = MJS_TASK_POINTMASS_REACH, KIND_REACH = MJS_TASK_ROBOT_REACH, KIND_PUSH2 = MJS_TASK_PLANAR_PUSH, KIND_BUTTON = MJS_TASK_BUTTON_PUSH, KIND_PUSH5, KIND_BUTTON_ARTICULATED };
+// The step launch a handle takes (launch<false>), named after what the grid is made of; resolve_instance has the reasons. Every
+// reset launch is its kind's one-wavefront kernel.
+enum Shape { SHAPE_ONE_WAVE, SHAPE_TWO_ROLES, SHAPE_THREE_WAVES, SHAPE_RESET_GROUPS, SHAPE_ENV_GROUPS, SHAPE_PUSH, SHAPE_PUSH_PREFETCH };
+
+constexpr int alg_bytes(int rows_read, int rows_written, int act_dim, int obs_dim) {
+  // state read + state written + flag byte r/w + action + obs + reward + discount + 5 flag bytes + ncon
+  return 8 * rows_read + 8 * rows_written + 2 + 8 * act_dim + 8 * obs_dim + (8 + 8 + 5 + 4);
+}
+
+struct Instance {
+  Kind kind;
+  int state_dim, obs_dim, act_dim;  // state rows (without the flag row), flat observation and action widths
+  int alg_bytes;                    // algorithmic HBM bytes of one env-step
+  int nprim;                        // render primitives per env (0: the scene is drawn without a list)
+  int prog_row;                     // Planar-Push: state row with the progress of the prepared next episode; -1 otherwise
+  // resolved per handle
+  Shape shape = SHAPE_ONE_WAVE;
+  int epw = 64;        // envs per workgroup where the kernel takes it as an argument (Button-Push, both grippers)
+  size_t lds_pad = 0;  // unused dynamic LDS per workgroup of the default Robot-Reach / Button-Push step launch (A/B builds only)
+};
+
+// Every layout constant of an instance, once; indexed by Kind. The per-task queries of the ABI describe the task's default instance.
+const Instance INSTANCES[] = {
+    {KIND_POINTMASS, pm::STATE_DIM, pm::OBS_DIM, pm::ACT_DIM, alg_bytes(pm::STATE_DIM, pm::STATE_DIM - 2 /*target unchanged*/, pm::ACT_DIM, pm::OBS_DIM), 0, -1},
+    // q v time target + carried cos / sin; the qacc_warmstart rows are only touched by the robust path
+    {KIND_REACH, rr::STATE_DIM, rr::OBS_DIM, rr::ACT_DIM, alg_bytes(rr::HOT_ROWS_READ, rr::HOT_ROWS_WRITTEN, rr::ACT_DIM, rr::OBS_DIM), rend::RR_NPRIM, -1},
+    // Planar-Push: one world's rows (the state also carries the prepared next episode, its progress row, the servo set-point and
+    // cos / sin); everything but the target is rewritten
+    {KIND_PUSH2, pp::FULL_STATE_DIM, pp::OBS_DIM, pp::ACT_DIM, alg_bytes(pp::STATE_DIM, pp::STATE_DIM - 3, pp::ACT_DIM, pp::OBS_DIM), rend::ARM_NREC + 1 + pp::NB, pp::PROG_ROW},
+    {KIND_BUTTON, bp::STATE_DIM, bp::OBS_DIM, bp::ACT_DIM_JOINT, alg_bytes(bp::HOT_ROWS_READ, bp::HOT_ROWS_WRITTEN, bp::ACT_DIM_JOINT, bp::OBS_DIM), rend::BP_NPRIM, -1},
+    {KIND_PUSH5, pp5::FULL_STATE_DIM, pp5::OBS_DIM, pp5::ACT_DIM, alg_bytes(pp5::STATE_DIM, pp5::STATE_DIM - 3, pp5::ACT_DIM, pp5::OBS_DIM), rend::ARM_NREC + 1 + pp5::NB, pp5::PROG_ROW},
+    {KIND_BUTTON_ARTICULATED, bg::STATE_DIM, bg::OBS_DIM, bp::ACT_DIM_JOINT, alg_bytes(bg::STATE_DIM, bg::STATE_DIM - 3, bp::ACT_DIM_JOINT, bg::OBS_DIM), rend::BP_NPRIM, -1},
+};
+static_assert(rend::ARM_NREC + 1 + pp5::NB == rend::PP_NPRIM, "the 5-slot instance fills the primitive list's capacity");
+
+#ifdef MJS_AB_KNOBS
+#include <cstdlib>
+// A/B knobs of diagnostic builds (tools/ab_build.py --flag=-DMJS_AB_KNOBS); the shipped library has none, a stray variable would change
+// the workgroup shape behind the bitwise guarantees of include/mjsim.h. Read once per mjs_create (the handle's device is current),
+// range-checked, stored in the instance; returns what is wrong with a value, or nullptr. MJS_LDS_PAD: a pad above half of the CU's
+// 160 KB leaves room for ONE workgroup per CU, which tells whether the dispatcher packs the few workgroups of a 4096-env launch
+// onto shared CUs (profiles/r04_e_workgroup_placement.txt). MJS_BP_EPG, MJS_BG_EPW: envs per workgroup (profiles/r04_d_*, r04_b_*).
+static const char* read_ab_knobs(Instance& in) {
+  const char* ev;
+  if ((in.kind == KIND_REACH || in.kind == KIND_BUTTON) && (ev = std::getenv("MJS_LDS_PAD"))) {
+    const void* kernel = in.kind == KIND_REACH ? reinterpret_cast<const void*>(&rr::kernel3<0>) : reinterpret_cast<const void*>(&bp::kernel<false, 2>);
+    const long pad = std::atol(ev);
+    hipFuncAttributes attr;
+    if (hipFuncGetAttributes(&attr, kernel) != hipSuccess || pad < 0 || (size_t)pad > (size_t)160 * 1024 - attr.sharedSizeBytes)
+      return "mjs_create: MJS_LDS_PAD is negative or exceeds the CU's 160 KB of LDS minus what the kernel uses";
+    if (pad > 0 && hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pad) != hipSuccess) return "mjs_create: MJS_LDS_PAD opt-in failed";
+    in.lds_pad = (size_t)pad;
+  }
+  if (in.kind == KIND_BUTTON && (ev = std::getenv("MJS_BP_EPG"))) {
+    in.epw = std::atoi(ev);
+    if (in.epw != 8 && in.epw != 16 && in.epw != 32 && in.epw != 64) return "mjs_create: MJS_BP_EPG must be 8, 16, 32 or 64";
+  }
+  if (in.kind == KIND_BUTTON_ARTICULATED && (ev = std::getenv("MJS_BG_EPW"))) {
+    in.epw = std::atoi(ev);
+    if (in.epw < 1 || in.epw > 16) return "mjs_create: MJS_BG_EPW must be 1..16";
+  }
+  return nullptr;
+}
+#else
+static const char* read_ab_knobs(Instance&) { return nullptr; }
+#endif
 
 struct mjs_handle {
   mjs_config cfg;
+  Instance inst;
   // render primitive list of the CURRENT state already built on this stream? (the visual configs render two cameras per
   // control step; reset / step / rollout / set_state invalidate)
   bool prims_valid = false;
   void* prims_stream = nullptr;
-  int state_dim, obs_dim, act_dim;
-  double* state;     // [state_dim][N]
-  uint8_t* flags;    // [N]
-  uint32_t* rng_mt;  // [624][N]
-  int32_t* rng_pos;  // [N]
-  unsigned long long* stamps;  // diagnostic builds only
-  float* prims;                // [N][nprim][PRIM_FLOATS] render primitive list (robot scenes)
+  double* state = nullptr;     // [state_dim][N]
+  uint8_t* flags = nullptr;    // [N]
+  uint32_t* rng_mt = nullptr;  // [624][N]
+  int32_t* rng_pos = nullptr;  // [N]
+  unsigned long long* stamps = nullptr;  // diagnostic builds only
+  float* prims = nullptr;      // [N][nprim][PRIM_FLOATS] render primitive list (robot scenes)
   float4* bg_ray = nullptr;    // [bg_H * bg_W] scene-camera ray table (rend::Background), built at the first render of a size
   uint32_t* bg_rgb = nullptr;
   int bg_H = 0, bg_W = 0;
-  float* cams;                 // [N][12] wrist-camera poses (Button-Push)
+  float* cams = nullptr;       // [N][12] wrist-camera poses (Button-Push)
   double* ws = nullptr;        // [rr::WS_ROWS][N] contact workspace of the general constraint stage (Robot-Reach, Button-Push)
   int epoch = 0;               // parity of the next step launch (FLAG_EPOCH)
   double* ws14 = nullptr;      // [bg::WS_DOUBLES][N] constraint rows of the articulated-gripper kernel (mjs_gripper14.h)
@@ -165,30 +238,59 @@ __global__ void tcp_to_joints_kernel(const double* pos, const double* guess, dou
   ok[i] = found;
 }
 
-// A/B knob (MJS_LDS_PAD = bytes of unused dynamic LDS per workgroup of the Robot-Reach / Button-Push step kernels): a pad above half of the
-// CU's 160 KB leaves room for ONE workgroup per CU, which tells whether the dispatcher packs the few workgroups of a 4096-env launch onto
-// shared CUs (profiles/r04_e_workgroup_placement.txt).
-size_t lds_pad() {
-  static const size_t pad = [] { const char* ev = std::getenv("MJS_LDS_PAD"); return ev ? (size_t)std::atol(ev) : (size_t)0; }();
-  return pad;
+// The instance a task's per-task queries describe, and the one its handles run unless the config widens it; nullptr: no such task
+const Instance* task_defaults(int task) { return task >= KIND_POINTMASS && task <= KIND_BUTTON ? &INSTANCES[task] : nullptr; }
+
+// What a handle runs, from its validated config (defaults filled in). Everything here is constant for the life of the handle.
+Instance resolve_instance(const mjs_config& cfg) {
+  Kind kind = task_defaults(cfg.task)->kind;
+  if (kind == KIND_BUTTON && cfg.gripper_model == MJS_GRIPPER_ARTICULATED) kind = KIND_BUTTON_ARTICULATED;
+  if (kind == KIND_PUSH2 && cfg.n_objects > MJS_PP_FAST_OBJECTS) kind = KIND_PUSH5;  // 3..5 blocks: the 5-slot instance
+  Instance in = INSTANCES[kind];
+  in.act_dim = mjs_action_dim_for(cfg.task, cfg.action_type);
+  const bool next_step = cfg.autoreset == MJS_AUTORESET_NEXT_STEP;
+  switch (kind) {
+    case KIND_POINTMASS: break;  // SHAPE_ONE_WAVE
+    case KIND_PUSH2:
+    case KIND_PUSH5:
+      // next episodes are prepared ahead of time by prefetch workgroups (mjs_push_impl.h NEXT_ROW0); variant 1 keeps round 3's
+      // behaviour (the settle steps of a reset run inside the step launch) for A/B measurements
+      in.shape = next_step && cfg.kernel_variant != MJS_VARIANT_SINGLE_WAVE ? SHAPE_PUSH_PREFETCH : SHAPE_PUSH;
+      break;
+    case KIND_BUTTON_ARTICULATED:
+      // One kernel shape (a workgroup resets its own envs, never reset groups). The kernel is bound by instruction DELIVERY (its
+      // substep streams ~150 KB of code through the instruction cache), so fewer, fuller wavefronts win as soon as every CU has one:
+      // 16 envs per workgroup (what the LDS holds: 16 x 9.8 KB) from 4096 envs on - 11.7 ms per launch against 14.9 with 4
+      // (profiles/r04_b_*)
+      in.shape = SHAPE_ENV_GROUPS;
+      in.epw = cfg.num_envs < 1024 ? 4 : cfg.num_envs < 4096 ? 8 : 16;
+      in.alg_bytes += 8 * (in.act_dim - INSTANCES[kind].act_dim);  // this instance counts the handle's action width
+      break;
+    case KIND_REACH:
+    case KIND_BUTTON:
+      // Button-Push: envs per workgroup = 64 (in.epw). Smaller groups were measured (profiles/r04_d_button_group_size.txt) and LOSE:
+      // with 16 envs per group the steady state goes 53 -> 84 us per launch and the desynchronised case stays at 260 us - four times
+      // the wavefronts share SIMDs (the dispatcher packs workgroups onto CUs), which costs more than the smaller groups save.
+      if (cfg.kernel_variant == MJS_VARIANT_SINGLE_WAVE) in.shape = SHAPE_ONE_WAVE;
+      // Robot-Reach, two shapes of the same step (results equal to rounding): an IK wave + two role-specialised dynamics waves per
+      // 64 envs is the faster one while every workgroup has a CU to itself (the launch is one workgroup's latency: -10 % at 4096
+      // envs); past 16384 envs per GPU the chip is full and the third, mostly idle wave costs a SIMD: the two-role kernel of round 1
+      // then has twice the throughput (profiles/r02_j_batch_size_scaling.txt: 65536 envs 435 vs 822 M env-steps/s).
+      else if (kind == KIND_REACH && (cfg.kernel_variant == MJS_VARIANT_TWO_ROLES || (cfg.kernel_variant == MJS_VARIANT_DEFAULT && cfg.num_envs > 16384)))
+        in.shape = SHAPE_TWO_ROLES;
+      // MJS_VARIANT_RESET_GROUPS, for episodes that end at different times: the second half of the grid are reset workgroups (one
+      // per 64 envs, on other CUs: an env whose episode ended is reset there while the first half steps the others: 54 -> 38 us per
+      // launch with 1 % of the envs ending in every step); the launch parity tells a freshly reset env from one that waits. Not the
+      // default for synchronous episodes: the 64 extra workgroups cost 0.9 us per launch at 4096 envs.
+      else if (cfg.kernel_variant == MJS_VARIANT_RESET_GROUPS && next_step) in.shape = SHAPE_RESET_GROUPS;
+      else in.shape = kind == KIND_REACH ? SHAPE_THREE_WAVES : SHAPE_TWO_ROLES;
+      break;
+  }
+  return in;
 }
-// Button-Push: envs per workgroup = 64. Smaller groups were measured (MJS_BP_EPG, profiles/r04_d_button_group_size.txt) and LOSE: with
-// 16 envs per group the steady state goes 53 -> 84 us per launch and the desynchronised case stays at 260 us - four times the
-// wavefronts share SIMDs (the dispatcher packs workgroups onto CUs), which costs more than the smaller groups save.
-int button_epg(const mjs_handle* h) {
-  if (h->cfg.task != MJS_TASK_BUTTON_PUSH) return 64;
-  if (const char* ev = std::getenv("MJS_BP_EPG")) { const int v = std::atoi(ev); if (v == 8 || v == 16 || v == 32 || v == 64) return v; }
-  return 64;
-}
-int push_prog_row(const mjs_handle* h) { return h->cfg.n_objects > MJS_PP_FAST_OBJECTS ? pp5::PROG_ROW : pp::PROG_ROW; }
-bool articulated(const mjs_handle* h) { return h->cfg.task == MJS_TASK_BUTTON_PUSH && h->cfg.gripper_model == MJS_GRIPPER_ARTICULATED; }
-bool uses_reset_groups(const mjs_handle* h) {
-  if (articulated(h)) return false;  // one kernel shape: a workgroup resets its own envs
-  return (h->cfg.task == MJS_TASK_ROBOT_REACH || h->cfg.task == MJS_TASK_BUTTON_PUSH) && h->cfg.kernel_variant == MJS_VARIANT_RESET_GROUPS &&
-         h->cfg.autoreset == MJS_AUTORESET_NEXT_STEP;
-}
+
 uint8_t host_pending_byte(const mjs_handle* h) {
-  return (uint8_t)(FLAG_RESET_PENDING | ((uses_reset_groups(h) && !h->epoch) ? FLAG_EPOCH : 0));
+  return (uint8_t)(FLAG_RESET_PENDING | ((h->inst.shape == SHAPE_RESET_GROUPS && !h->epoch) ? FLAG_EPOCH : 0));
 }
 
 KernelParams make_params(const mjs_handle* h, const double* actions, const uint8_t* mask, const mjs_outputs* out) {
@@ -203,11 +305,9 @@ KernelParams make_params(const mjs_handle* h, const double* actions, const uint8
   p.max_episode_steps = h->cfg.max_episode_steps;
   p.block_shape = h->cfg.block_shape;
   p.epoch = h->epoch;
-  p.reset_groups = uses_reset_groups(h);
-  p.epg = button_epg(h);
-  // Planar-Push: next episodes are prepared ahead of time by prefetch workgroups (mjs_push_impl.h NEXT_ROW0); variant 1 keeps
-  // round 3's behaviour (the settle steps of a reset run inside the step launch) for A/B measurements
-  p.prefetch = h->cfg.task == MJS_TASK_PLANAR_PUSH && h->cfg.autoreset == MJS_AUTORESET_NEXT_STEP && h->cfg.kernel_variant != MJS_VARIANT_SINGLE_WAVE;
+  p.reset_groups = h->inst.shape == SHAPE_RESET_GROUPS;
+  p.epg = h->inst.kind == KIND_BUTTON ? h->inst.epw : 64;
+  p.prefetch = h->inst.shape == SHAPE_PUSH_PREFETCH;
   p.time_limit = h->cfg.time_limit;
   p.state = h->state;
   p.flags = h->flags;
@@ -220,56 +320,38 @@ KernelParams make_params(const mjs_handle* h, const double* actions, const uint8
   return p;
 }
 
-// envs per workgroup of the articulated-gripper kernel. The kernel is bound by instruction DELIVERY (its substep streams ~150 KB of
-// code through the instruction cache), so fewer, fuller wavefronts win as soon as every CU has one: 16 envs per workgroup (what
-// the LDS holds: 16 x 9.8 KB) from 4096 envs on - 11.7 ms per launch against 14.9 with 4 (profiles/r04_b_*)
-int bg_epw_for(int n) {
-  if (const char* ev = std::getenv("MJS_BG_EPW")) { const int v = std::atoi(ev); if (v >= 1 && v <= 16) return v; }  // A/B experiments
-  return n < 1024 ? 4 : n < 4096 ? 8 : 16;
-}
-
 constexpr int BLOCK = 64;  // one wavefront per workgroup: N/64 workgroups spread over the CUs
 inline dim3 grid_for(int n) { return dim3((unsigned)((n + BLOCK - 1) / BLOCK)); }
 
 template <bool IS_RESET>
 int launch(mjs_handle* h, const KernelParams& p, hipStream_t s) {
-  bool flip_epoch = false;
-  if (h->cfg.task == MJS_TASK_POINTMASS_REACH) pm::kernel<IS_RESET><<<grid_for(p.N), BLOCK, 0, s>>>(p);
-  else if (h->cfg.task == MJS_TASK_PLANAR_PUSH && h->cfg.n_objects <= MJS_PP_FAST_OBJECTS)
-    pp::kernel<IS_RESET><<<dim3((unsigned)(((!IS_RESET && p.prefetch) ? 2 : 1) * ((p.N + pp::EPW * pp::WAVES - 1) / (pp::EPW * pp::WAVES)))), BLOCK * pp::WAVES, pp::LDS_BYTES, s>>>(p);
-  else if (h->cfg.task == MJS_TASK_PLANAR_PUSH)  // 3..5 blocks: the 5-slot instance, its cooperative workspace needs the large-LDS opt-in (mjs_create)
-    pp5::kernel<IS_RESET><<<dim3((unsigned)(((!IS_RESET && p.prefetch) ? 2 : 1) * ((p.N + pp5::EPW * pp5::WAVES - 1) / (pp5::EPW * pp5::WAVES)))), BLOCK * pp5::WAVES, pp5::LDS_BYTES, s>>>(p);
-  else if (articulated(h)) {
-    const int epw = bg_epw_for(p.N);
-    bg::kernel<IS_RESET><<<dim3((unsigned)((p.N + epw - 1) / epw)), IS_RESET ? BLOCK : bg::ROLES * BLOCK, (size_t)epw * sizeof(bg::Env), s>>>(p, h->ws14, epw);  // stepping: bg::ROLES wavefronts share the envs
+  const Instance& in = h->inst;
+  const Shape shape = IS_RESET ? SHAPE_ONE_WAVE : in.shape;  // Robot-Reach / Button-Push reset on their one-wavefront kernel
+  const dim3 bgrid((unsigned)((p.N + p.epg - 1) / p.epg));   // Button-Push
+  switch (in.kind) {
+    case KIND_POINTMASS: pm::kernel<IS_RESET><<<grid_for(p.N), BLOCK, 0, s>>>(p); break;
+    case KIND_PUSH2: pp::kernel<IS_RESET><<<dim3((unsigned)(((!IS_RESET && p.prefetch) ? 2 : 1) * ((p.N + pp::EPW * pp::WAVES - 1) / (pp::EPW * pp::WAVES)))), BLOCK * pp::WAVES, pp::LDS_BYTES, s>>>(p); break;
+    case KIND_PUSH5: pp5::kernel<IS_RESET><<<dim3((unsigned)(((!IS_RESET && p.prefetch) ? 2 : 1) * ((p.N + pp5::EPW * pp5::WAVES - 1) / (pp5::EPW * pp5::WAVES)))), BLOCK * pp5::WAVES, pp5::LDS_BYTES, s>>>(p); break;
+    case KIND_BUTTON_ARTICULATED:  // stepping: bg::ROLES wavefronts share the envs
+      bg::kernel<IS_RESET><<<dim3((unsigned)((p.N + in.epw - 1) / in.epw)), IS_RESET ? BLOCK : bg::ROLES * BLOCK, (size_t)in.epw * sizeof(bg::Env), s>>>(p, h->ws14, in.epw); break;
+    case KIND_BUTTON:
+      switch (shape) {
+        case SHAPE_ONE_WAVE: bp::kernel<IS_RESET, 1><<<bgrid, BLOCK, 0, s>>>(p); break;
+        case SHAPE_RESET_GROUPS: bp::kernel<false, 2><<<dim3(2 * bgrid.x), 2 * BLOCK, 0, s>>>(p); break;
+        default: bp::kernel<false, 2><<<bgrid, 2 * BLOCK, in.lds_pad, s>>>(p); break;  // SHAPE_TWO_ROLES
+      }
+      break;
+    case KIND_REACH:
+      switch (shape) {
+        case SHAPE_ONE_WAVE: rr::kernel<IS_RESET, 1><<<grid_for(p.N), BLOCK, 0, s>>>(p); break;
+        case SHAPE_TWO_ROLES: rr::kernel<false, 2><<<grid_for(p.N), 2 * BLOCK, 0, s>>>(p); break;
+        case SHAPE_RESET_GROUPS: rr::kernel3<0><<<dim3(2 * grid_for(p.N).x), 3 * BLOCK, 0, s>>>(p); break;
+        default: rr::kernel3<0><<<grid_for(p.N), 3 * BLOCK, in.lds_pad, s>>>(p); break;  // SHAPE_THREE_WAVES
+      }
+      break;
   }
-  else if (h->cfg.task == MJS_TASK_BUTTON_PUSH) {
-    const dim3 bgrid((unsigned)((p.N + p.epg - 1) / p.epg));
-    if (IS_RESET || h->cfg.kernel_variant == MJS_VARIANT_SINGLE_WAVE) bp::kernel<IS_RESET, 1><<<bgrid, BLOCK, 0, s>>>(p);
-    else if (p.reset_groups) {  // MJS_VARIANT_RESET_GROUPS: the second half of the grid resets the envs whose episode ended
-      bp::kernel<false, 2><<<dim3(2 * bgrid.x), 2 * BLOCK, 0, s>>>(p);
-      flip_epoch = true;
-    }
-    else bp::kernel<false, 2><<<bgrid, 2 * BLOCK, lds_pad(), s>>>(p);
-  }
-  else if (IS_RESET || h->cfg.kernel_variant == MJS_VARIANT_SINGLE_WAVE) rr::kernel<IS_RESET, 1><<<grid_for(p.N), BLOCK, 0, s>>>(p);
-  // Two shapes of the same step (results equal to rounding): an IK wave + two role-specialised dynamics waves per 64 envs
-  // is the faster one while every workgroup has a CU to itself (the launch is one workgroup's latency: -10 % at 4096 envs);
-  // past 16384 envs per GPU the chip is full and the third, mostly idle wave costs a SIMD: the two-role kernel of round 1
-  // then has twice the throughput (profiles/r02_j_batch_size_scaling.txt: 65536 envs 435 vs 822 M env-steps/s).
-  else if (h->cfg.kernel_variant == MJS_VARIANT_TWO_ROLES || (h->cfg.kernel_variant == MJS_VARIANT_DEFAULT && p.N > 16384))
-    rr::kernel<false, 2><<<grid_for(p.N), 2 * BLOCK, 0, s>>>(p);
-  else if (p.reset_groups) {
-    // MJS_VARIANT_RESET_GROUPS, for episodes that end at different times: the second half of the grid are reset workgroups
-    // (one per 64 envs, on other CUs: an env whose episode ended is reset there while the first half steps the others: 54 -> 38 us
-    // per launch with 1 % of the envs ending in every step); the launch parity tells a freshly reset env from one that waits.
-    // Not the default for synchronous episodes: the 64 extra workgroups cost 0.9 us per launch at 4096 envs.
-    rr::kernel3<0><<<dim3(2 * grid_for(p.N).x), 3 * BLOCK, 0, s>>>(p);
-    flip_epoch = true;
-  }
-  else rr::kernel3<0><<<grid_for(p.N), 3 * BLOCK, lds_pad(), s>>>(p);
   HIP_TRY(h, hipGetLastError());
-  if (flip_epoch) h->epoch ^= 1;  // only a launch that was accepted consumed its parity
+  if (shape == SHAPE_RESET_GROUPS) h->epoch ^= 1;  // only a launch that was accepted consumed its parity
   return MJS_OK;
 }
 
@@ -284,46 +366,33 @@ extern "C" {
 #define MJS_STR(x) MJS_STR2(x)
 const char* mjs_version(void) { return "mjsim-hip 0.3 (gfx950, abi " MJS_STR(MJS_ABI_VERSION) ") src=" MJS_SOURCE_HASH; }
 
-int mjs_obs_dim(int task) {
-  return task == MJS_TASK_POINTMASS_REACH ? pm::OBS_DIM : task == MJS_TASK_ROBOT_REACH ? rr::OBS_DIM : task == MJS_TASK_BUTTON_PUSH ? bp::OBS_DIM : task == MJS_TASK_PLANAR_PUSH ? pp::OBS_DIM : -1;
-}
+int mjs_obs_dim(int task) { const Instance* d = task_defaults(task); return d ? d->obs_dim : -1; }
 int mjs_action_dim_for(int task, int action_type) {
   if (task == MJS_TASK_BUTTON_PUSH) return action_type == MJS_ACTION_ABS_EEF ? bp::ACT_DIM_EEF : action_type == MJS_ACTION_ABS_JOINT ? bp::ACT_DIM_JOINT : -1;
-  return task == MJS_TASK_POINTMASS_REACH ? pm::ACT_DIM : task == MJS_TASK_ROBOT_REACH ? rr::ACT_DIM : task == MJS_TASK_PLANAR_PUSH ? pp::ACT_DIM : -1;
+  const Instance* d = task_defaults(task);
+  return d ? d->act_dim : -1;
 }
 int mjs_action_dim(int task) { return mjs_action_dim_for(task, MJS_ACTION_ABS_JOINT); }
-int mjs_state_dim(int task) {
-  return task == MJS_TASK_POINTMASS_REACH ? pm::STATE_DIM + 1 : task == MJS_TASK_ROBOT_REACH ? rr::STATE_DIM + 1 : task == MJS_TASK_BUTTON_PUSH ? bp::STATE_DIM + 1 : task == MJS_TASK_PLANAR_PUSH ? pp::FULL_STATE_DIM + 1 : -1;
-}
-int mjs_env_obs_dim(const mjs_handle* h) { return h ? h->obs_dim : -1; }
-int mjs_env_state_dim(const mjs_handle* h) { return h ? h->state_dim + 1 : -1; }
-int mjs_substeps(int task) {
-  return task == MJS_TASK_POINTMASS_REACH ? MJS_PM_NSUB : (task == MJS_TASK_ROBOT_REACH || task == MJS_TASK_BUTTON_PUSH || task == MJS_TASK_PLANAR_PUSH) ? MJS_RR_NSUB : -1;
-}
-
-int mjs_algorithmic_bytes_per_env_step(int task) {
-  // state read + state written + flag byte r/w + action + obs + reward + discount + 5 flag bytes + ncon
-  const int out_fixed = 8 + 8 + 5 + 4;
-  if (task == MJS_TASK_POINTMASS_REACH)
-    return 8 * pm::STATE_DIM /*R*/ + 8 * (pm::STATE_DIM - 2) /*W: target unchanged*/ + 2 + 8 * pm::ACT_DIM + 8 * pm::OBS_DIM + out_fixed;
-  if (task == MJS_TASK_ROBOT_REACH)
-    return 8 * rr::HOT_ROWS_READ + 8 * rr::HOT_ROWS_WRITTEN + 2 + 8 * rr::ACT_DIM + 8 * rr::OBS_DIM + out_fixed;  // q v time target + carried cos / sin; the qacc_warmstart rows are only touched by the robust path
-  if (task == MJS_TASK_PLANAR_PUSH)  // everything but the target is rewritten
-    return 8 * pp::STATE_DIM /*R*/ + 8 * (pp::STATE_DIM - 3) /*W*/ + 2 + 8 * pp::ACT_DIM + 8 * pp::OBS_DIM + out_fixed;
-  if (task == MJS_TASK_BUTTON_PUSH)
-    return 8 * bp::HOT_ROWS_READ + 8 * bp::HOT_ROWS_WRITTEN + 2 + 8 * bp::ACT_DIM_JOINT + 8 * bp::OBS_DIM + out_fixed;
-  return -1;
-}
+int mjs_state_dim(int task) { const Instance* d = task_defaults(task); return d ? d->state_dim + 1 : -1; }
+int mjs_algorithmic_bytes_per_env_step(int task) { const Instance* d = task_defaults(task); return d ? d->alg_bytes : -1; }
+int mjs_env_obs_dim(const mjs_handle* h) { return h ? h->inst.obs_dim : -1; }
+int mjs_env_state_dim(const mjs_handle* h) { return h ? h->inst.state_dim + 1 : -1; }
+int mjs_env_algorithmic_bytes_per_env_step(const mjs_handle* h) { return h ? h->inst.alg_bytes : -1; }
+int mjs_substeps(int task) { return task == MJS_TASK_POINTMASS_REACH ? MJS_PM_NSUB : task_defaults(task) ? MJS_RR_NSUB : -1; }
 
 const char* mjs_last_error(const mjs_handle* h) { return h ? h->err.c_str() : g_err.c_str(); }
+
+// a failing step of mjs_create: the scope guard there frees what the handle holds so far
+#define CREATE_TRY(what, expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return hip_fail(nullptr, e_, "mjs_create: " what); } while (0)
+#define LDS_OPT_IN(what, kernel, bytes) \
+  CREATE_TRY(what, hipFuncSetAttribute(reinterpret_cast<const void*>(&kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(bytes)))
 
 int mjs_create(const mjs_config* cfg, mjs_handle** out) {
   if (!cfg || !out) return fail(nullptr, MJS_ERR_INVALID_ARG, "mjs_create: null argument");
   *out = nullptr;
   if (cfg->struct_size != sizeof(mjs_config))
     return fail(nullptr, MJS_ERR_INVALID_ARG, "mjs_create: mjs_config.struct_size does not match this library's header (abi " MJS_STR(MJS_ABI_VERSION) "): the caller was built against another include/mjsim.h");
-  if (cfg->task != MJS_TASK_POINTMASS_REACH && cfg->task != MJS_TASK_ROBOT_REACH && cfg->task != MJS_TASK_BUTTON_PUSH && cfg->task != MJS_TASK_PLANAR_PUSH)
-    return fail(nullptr, MJS_ERR_UNSUPPORTED, "mjs_create: unknown task id");
+  if (!task_defaults(cfg->task)) return fail(nullptr, MJS_ERR_UNSUPPORTED, "mjs_create: unknown task id");
   if (mjs_action_dim_for(cfg->task, cfg->action_type) < 0) return fail(nullptr, MJS_ERR_INVALID_ARG, "mjs_create: bad action_type");
   if (cfg->gripper_model != MJS_GRIPPER_REDUCED && cfg->gripper_model != MJS_GRIPPER_ARTICULATED) return fail(nullptr, MJS_ERR_INVALID_ARG, "mjs_create: bad gripper_model");
   if (cfg->gripper_model == MJS_GRIPPER_ARTICULATED && cfg->task != MJS_TASK_BUTTON_PUSH)
@@ -338,142 +407,66 @@ int mjs_create(const mjs_config* cfg, mjs_handle** out) {
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
     return fail(nullptr, MJS_ERR_NO_DEVICE, "mjs_create: no HIP device visible (this library has no CPU path)");
   if (cfg->device < 0 || cfg->device >= ndev) return fail(nullptr, MJS_ERR_INVALID_ARG, "mjs_create: device ordinal out of range");
-  mjs_handle* h = new (std::nothrow) mjs_handle();
+  DeviceGuard dev_(cfg->device);  // ahead of the handle's guard: a failed create frees the handle while its device is still selected
+  std::unique_ptr<mjs_handle, void (*)(mjs_handle*)> guard(new (std::nothrow) mjs_handle(), mjs_destroy);  // every early return cleans up
+  mjs_handle* h = guard.get();
   if (!h) return fail(nullptr, MJS_ERR_ALLOC, "mjs_create: out of host memory");
   h->cfg = *cfg;
   if (h->cfg.reward_type < 0) h->cfg.reward_type = default_reward(cfg->task);
   if (h->cfg.n_objects <= 0) h->cfg.n_objects = MJS_PP_FAST_OBJECTS;
   if (h->cfg.max_episode_steps <= 0) h->cfg.max_episode_steps = MJS_PP_MAX_CONTROL_STEPS;
   if (!(h->cfg.time_limit > 0)) h->cfg.time_limit = default_time_limit(cfg->task);
-  h->state_dim = mjs_state_dim(cfg->task) - 1;
-  h->obs_dim = mjs_obs_dim(cfg->task);
-  if (cfg->task == MJS_TASK_PLANAR_PUSH && h->cfg.n_objects > MJS_PP_FAST_OBJECTS) { h->state_dim = pp5::FULL_STATE_DIM; h->obs_dim = pp5::OBS_DIM; }
-  if (cfg->task == MJS_TASK_BUTTON_PUSH && h->cfg.gripper_model == MJS_GRIPPER_ARTICULATED) h->state_dim = bg::STATE_DIM;
-  h->act_dim = mjs_action_dim_for(cfg->task, cfg->action_type);
-  h->state = nullptr; h->flags = nullptr; h->rng_mt = nullptr; h->rng_pos = nullptr; h->stamps = nullptr; h->prims = nullptr; h->cams = nullptr;
+  h->inst = resolve_instance(h->cfg);
+  const Instance& in = h->inst;
   const size_t N = (size_t)cfg->num_envs;
-  DeviceGuard dev_(cfg->device);
-  hipError_t e = dev_.err;
-  if (e == hipSuccess && cfg->task == MJS_TASK_PLANAR_PUSH) {
-    // > 64 KB of dynamic LDS per workgroup is an opt-in (gfx950 has 160 KB per CU): cooperative workspaces + hull tables
+  CREATE_TRY("device allocation", dev_.err);
+  if (const char* bad_knob = read_ab_knobs(h->inst)) return fail(nullptr, MJS_ERR_INVALID_ARG, bad_knob);
+  // > 64 KB of dynamic LDS per workgroup is an opt-in (gfx950 has 160 KB per CU): Planar-Push's cooperative workspaces + hull tables,
+  // 16 envs per workgroup of the articulated-gripper kernel at large batches
 #ifndef MJS_STAMPS  // the diagnostic build's phase counters live in the env slots: its 5-slot instance does not fit and is not used
-    static_assert(pp5::LDS_BYTES <= 160 * 1024, "cooperative workspace exceeds the CU's LDS");
+  static_assert(pp5::LDS_BYTES <= 160 * 1024, "cooperative workspace exceeds the CU's LDS");
 #endif
-    static_assert(pp::LDS_BYTES <= 160 * 1024, "cooperative workspace exceeds the CU's LDS");
-    if (h->cfg.n_objects > MJS_PP_FAST_OBJECTS) {
-      e = hipFuncSetAttribute(reinterpret_cast<const void*>(&pp5::kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pp5::LDS_BYTES);
-      if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&pp5::kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pp5::LDS_BYTES);
-    } else {
-      e = hipFuncSetAttribute(reinterpret_cast<const void*>(&pp::kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pp::LDS_BYTES);
-      if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&pp::kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pp::LDS_BYTES);
-    }
-  }
-  if (e == hipSuccess) e = hipMalloc(&h->state, sizeof(double) * h->state_dim * N);
-  if (e == hipSuccess) e = hipMalloc(&h->flags, N);
-  if (e == hipSuccess) e = hipMalloc(&h->rng_mt, sizeof(uint32_t) * 624 * N);
-  if (e == hipSuccess) e = hipMalloc(&h->rng_pos, sizeof(int32_t) * N);
-  if (e == hipSuccess) e = hipMemset(h->state, 0, sizeof(double) * h->state_dim * N);
-  if (e == hipSuccess && cfg->task == MJS_TASK_ROBOT_REACH)  // render primitive list (no allocation in launch paths)
-    e = hipMalloc(&h->prims, sizeof(float) * rend::PRIM_FLOATS * rend::RR_NPRIM * N);
-  if (e == hipSuccess && cfg->task == MJS_TASK_BUTTON_PUSH) e = hipMalloc(&h->prims, sizeof(float) * rend::PRIM_FLOATS * rend::BP_NPRIM * N);
-  if (e == hipSuccess && cfg->task == MJS_TASK_PLANAR_PUSH) e = hipMalloc(&h->prims, sizeof(float) * rend::PRIM_FLOATS * rend::PP_NPRIM * N);
-  if (e == hipSuccess && cfg->task == MJS_TASK_BUTTON_PUSH) e = hipMalloc(&h->cams, sizeof(float) * 12 * N);
-  if (e == hipSuccess && articulated(h)) e = hipMalloc(&h->ws14, sizeof(double) * (size_t)bg::WS_DOUBLES * N);  // 15 KB per env: every row of every env
-  if (e == hipSuccess && cfg->task != MJS_TASK_POINTMASS_REACH)  // 3.4 KB per env, touched only by lanes with an arm geom in the floor
-    e = hipMalloc(&h->ws, sizeof(double) * rr::WS_ROWS * N);
+  static_assert(pp::LDS_BYTES <= 160 * 1024, "cooperative workspace exceeds the CU's LDS");
+  static_assert(16 * sizeof(bg::Env) <= 160 * 1024, "16 envs per workgroup fit the CU's LDS");
+  if (in.kind == KIND_PUSH2) { LDS_OPT_IN("device allocation", pp::kernel<false>, pp::LDS_BYTES); LDS_OPT_IN("device allocation", pp::kernel<true>, pp::LDS_BYTES); }
+  if (in.kind == KIND_PUSH5) { LDS_OPT_IN("device allocation", pp5::kernel<false>, pp5::LDS_BYTES); LDS_OPT_IN("device allocation", pp5::kernel<true>, pp5::LDS_BYTES); }
+  CREATE_TRY("device allocation", hipMalloc(&h->state, sizeof(double) * in.state_dim * N));
+  CREATE_TRY("device allocation", hipMalloc(&h->flags, N));
+  CREATE_TRY("device allocation", hipMalloc(&h->rng_mt, sizeof(uint32_t) * 624 * N));
+  CREATE_TRY("device allocation", hipMalloc(&h->rng_pos, sizeof(int32_t) * N));
+  CREATE_TRY("device allocation", hipMemset(h->state, 0, sizeof(double) * in.state_dim * N));
+  if (in.nprim) CREATE_TRY("device allocation", hipMalloc(&h->prims, sizeof(float) * rend::PRIM_FLOATS * in.nprim * N));  // no allocation in launch paths
+  if (cfg->task == MJS_TASK_BUTTON_PUSH) CREATE_TRY("device allocation", hipMalloc(&h->cams, sizeof(float) * 12 * N));
+  if (in.kind == KIND_BUTTON_ARTICULATED) CREATE_TRY("device allocation", hipMalloc(&h->ws14, sizeof(double) * (size_t)bg::WS_DOUBLES * N));  // 15 KB per env: every row of every env
+  if (in.kind != KIND_POINTMASS)  // 3.4 KB per env, touched only by lanes with an arm geom in the floor
+    CREATE_TRY("device allocation", hipMalloc(&h->ws, sizeof(double) * rr::WS_ROWS * N));
 #ifdef MJS_STAMPS
-  if (e == hipSuccess) e = hipMalloc(&h->stamps, sizeof(unsigned long long) * 16 * N);  // one slot block per workgroup, at most N workgroups
-  if (e == hipSuccess) e = hipMemset(h->stamps, 0, sizeof(unsigned long long) * 16 * N);
+  CREATE_TRY("device allocation", hipMalloc(&h->stamps, sizeof(unsigned long long) * 16 * N));  // one slot block per workgroup, at most N workgroups
+  CREATE_TRY("device allocation", hipMemset(h->stamps, 0, sizeof(unsigned long long) * 16 * N));
 #endif
-  if (e != hipSuccess) {
-    int rc = hip_fail(nullptr, e, "mjs_create: device allocation");
-    mjs_destroy(h);
-    return rc;
-  }
-  if (lds_pad() > 0) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&rr::kernel3<0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_pad());
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&bp::kernel<false, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_pad());
-  }
-  if (articulated(h)) {  // > 64 KB of dynamic LDS per workgroup is an opt-in (16 envs per workgroup at large batches)
-    static_assert(16 * sizeof(bg::Env) <= 160 * 1024, "16 envs per workgroup fit the CU's LDS");
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&bg::kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(16 * sizeof(bg::Env)));
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&bg::kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(16 * sizeof(bg::Env)));
-    if (e != hipSuccess) {
-      int rc = hip_fail(nullptr, e, "mjs_create: LDS opt-in");
-      mjs_destroy(h);
-      return rc;
-    }
-  }
-  if (articulated(h)) {  // the compiled 14-body model: a __device__ global of this device, the same constants for every handle
+  if (in.kind == KIND_BUTTON_ARTICULATED) {
+    LDS_OPT_IN("LDS opt-in", bg::kernel<false>, 16 * sizeof(bg::Env));
+    LDS_OPT_IN("LDS opt-in", bg::kernel<true>, 16 * sizeof(bg::Env));
+    // the compiled 14-body model: a __device__ global of this device, the same constants for every handle
     static const bg::Model host_model = [] { bg::Model m; std::memset(&m, 0, sizeof m); bg::build_model(m); return m; }();
-    e = hipMemcpyToSymbol(HIP_SYMBOL(bg::g_model), &host_model, sizeof host_model);
-    if (e != hipSuccess) {
-      int rc = hip_fail(nullptr, e, "mjs_create: model upload");
-      mjs_destroy(h);
-      return rc;
-    }
+    CREATE_TRY("model upload", hipMemcpyToSymbol(HIP_SYMBOL(bg::g_model), &host_model, sizeof host_model));
   }
   init_kernel<<<grid_for((int)N), BLOCK>>>(h->state, h->flags, (int)N, cfg->task, host_pending_byte(h));
-  if (cfg->task == MJS_TASK_PLANAR_PUSH) fill_row_kernel<<<grid_for((int)N), BLOCK>>>(h->state + (size_t)push_prog_row(h) * N, (int)N, -1.0);  // no next episode prepared
+  if (in.prog_row >= 0) fill_row_kernel<<<grid_for((int)N), BLOCK>>>(h->state + (size_t)in.prog_row * N, (int)N, -1.0);  // no next episode prepared
   seed_kernel<<<grid_for((int)N), BLOCK>>>(DevRng{h->rng_mt, h->rng_pos, (int)N}, 0u, cfg->env_index_offset);
-  e = hipDeviceSynchronize();
-  if (e != hipSuccess) {
-    int rc = hip_fail(nullptr, e, "mjs_create: init kernels");
-    mjs_destroy(h);
-    return rc;
-  }
-  *out = h;
+  CREATE_TRY("init kernels", hipDeviceSynchronize());
+  *out = guard.release();
   return MJS_OK;
 }
 
-void mjs_destroy(mjs_handle* h) {
+void mjs_destroy(mjs_handle* h) {  // the one place that frees what a handle owns
   if (!h) return;
 #ifdef MJS_STAMPS
-  if (h->stamps) {  // diagnostic build: mean phase lengths (shader cycles) of the LAST step launch
-    const int W = (h->cfg.num_envs + 63) / 64;
-    unsigned long long* host = new unsigned long long[16 * (size_t)h->cfg.num_envs];
-    (void)hipDeviceSynchronize();
-    (void)hipMemcpy(host, h->stamps, sizeof(unsigned long long) * 16 * (size_t)h->cfg.num_envs, hipMemcpyDeviceToHost);
-    double d[5] = {0, 0, 0, 0, 0}, e[5] = {0, 0, 0, 0, 0};
-    for (int w = 0; w < W; w++) {
-      for (int k = 0; k < 5; k++) d[k] += (double)(host[16 * w + k + 1] - host[16 * w + k]) / W;
-      for (int k = 0; k < 5; k++) e[k] += (double)(host[16 * w + 8 + k + 1] - host[16 * w + 8 + k]) / W;
-    }
-    if (h->cfg.task == MJS_TASK_PLANAR_PUSH) {
-      double c[16] = {0}, worst[16] = {0}, worst_total = 0;
-      int hist[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-      const int WG = (h->cfg.num_envs + pp::EPW * pp::WAVES - 1) / (pp::EPW * pp::WAVES);
-      for (int w = 0; w < WG; w++) {
-        double tot = 0;
-        for (int k = 0; k < 5; k++) tot += (double)host[16 * w + k];
-        for (int k = 0; k < 16; k++) c[k] += (double)host[16 * w + k] / WG;
-        if (tot > worst_total) { worst_total = tot; for (int k = 0; k < 16; k++) worst[k] = (double)host[16 * w + k]; }
-        const int ns = (int)host[16 * w + 6];
-        hist[ns == 0 ? 0 : ns <= 5 ? 1 : ns <= 10 ? 2 : ns <= 20 ? 3 : ns <= 30 ? 4 : ns <= 40 ? 5 : ns <= 60 ? 6 : ns <= 80 ? 7 : 8]++;
-      }
-      std::fprintf(stderr, "[MJS_STAMPS] planar-push, wave 0 of each workgroup, cycles per control step, MEAN: detect %.0f | arm dynamics %.0f | decoupled solves %.0f | cooperative coupled %.0f (of which the owner lane's publish %.0f) | integrate %.0f\n", c[0], c[1], c[2], c[3], c[5], c[4]);
-      std::fprintf(stderr, "[MJS_STAMPS] cooperative solves per wavefront and control step: mean %.2f (%.2f Newton iterations each), slowest wavefront %.0f solves / %.0f iterations; wavefronts with 0 | 1-5 | 6-10 | 11-20 | 21-30 | 31-40 | 41-60 | 61-80 | >80 solves: %d %d %d %d %d %d %d %d %d\n", c[6], c[6] > 0 ? c[7] / c[6] : 0.0, worst[6], worst[7], hist[0], hist[1], hist[2], hist[3], hist[4], hist[5], hist[6], hist[7], hist[8]);
-      std::fprintf(stderr, "[MJS_STAMPS] slowest wavefront, inside its cooperative solves: rows %.0f | init (M^-1 f, J a, update) %.0f | gradient+Hessian %.0f | Cholesky+solves %.0f | M v, J v %.0f | line search %.0f | update+gradient norm %.0f | J^T f %.0f\n", worst[15], worst[8], worst[9], worst[10], worst[11], worst[12], worst[13], worst[14]);
-      std::fprintf(stderr, "[MJS_STAMPS] SLOWEST workgroup: detect %.0f | arm dynamics %.0f | decoupled solves %.0f | cooperative coupled %.0f (publish %.0f) | integrate %.0f\n", worst[0], worst[1], worst[2], worst[3], worst[5], worst[4]);
-    }
-    double own = 0;  // Robot-Reach kernel3: stamp 6 = wave 0 has finished its own prologue (load, sincos, substep 0) and reaches the IK barrier
-    for (int w = 0; w < W; w++) own += (double)(host[16 * w + 6] - host[16 * w + 0]) / W;
-    std::fprintf(stderr, "[MJS_STAMPS] cycles: load+IK %.0f (of which wave 0's own load + sincos + substep 0: %.0f) | substeps %.0f | fk+obs %.0f | contacts %.0f | store %.0f\n", d[0], own, d[1], d[2], d[3], d[4]);
-    std::fprintf(stderr, "[MJS_STAMPS] role-0 substep 10: CRBA+factor+invert %.0f | barrier %.0f | apply inverse+publish+barrier %.0f | integrate %.0f\n", e[0], e[1], e[2], e[3]);
-    delete[] host;
-    (void)hipFree(h->stamps);
-  }
+  if (h->stamps) mjs_stamps_report(h->stamps, h->cfg.num_envs, h->cfg.task);
 #endif
-  if (h->state) (void)hipFree(h->state);
-  if (h->flags) (void)hipFree(h->flags);
-  if (h->rng_mt) (void)hipFree(h->rng_mt);
-  if (h->rng_pos) (void)hipFree(h->rng_pos);
-  if (h->prims) (void)hipFree(h->prims);
-  if (h->bg_ray) (void)hipFree(h->bg_ray);
-  if (h->bg_rgb) (void)hipFree(h->bg_rgb);
-  if (h->cams) (void)hipFree(h->cams);
-  if (h->ws) (void)hipFree(h->ws);
-  if (h->ws14) (void)hipFree(h->ws14);
+  for (void* p : {(void*)h->state, (void*)h->flags, (void*)h->rng_mt, (void*)h->rng_pos, (void*)h->stamps, (void*)h->prims, (void*)h->bg_ray, (void*)h->bg_rgb,
+                  (void*)h->cams, (void*)h->ws, (void*)h->ws14})
+    if (p) (void)hipFree(p);
   delete h;
 }
 
@@ -483,8 +476,8 @@ int mjs_seed(mjs_handle* h, uint32_t base_seed, void* stream) {
   HIP_TRY(h, dev_.err);
   seed_kernel<<<grid_for(h->cfg.num_envs), BLOCK, 0, (hipStream_t)stream>>>(DevRng{h->rng_mt, h->rng_pos, h->cfg.num_envs}, base_seed,
                                                                            h->cfg.env_index_offset);
-  if (h->cfg.task == MJS_TASK_PLANAR_PUSH)  // episodes prepared from the old streams are void
-    fill_row_kernel<<<grid_for(h->cfg.num_envs), BLOCK, 0, (hipStream_t)stream>>>(h->state + (size_t)push_prog_row(h) * h->cfg.num_envs, h->cfg.num_envs, -1.0);
+  if (h->inst.prog_row >= 0)  // Planar-Push: episodes prepared from the old streams are void
+    fill_row_kernel<<<grid_for(h->cfg.num_envs), BLOCK, 0, (hipStream_t)stream>>>(h->state + (size_t)h->inst.prog_row * h->cfg.num_envs, h->cfg.num_envs, -1.0);
   HIP_TRY(h, hipGetLastError());
   return MJS_OK;
 }
@@ -518,8 +511,8 @@ int mjs_rollout(mjs_handle* h, const double* actions_dev, int32_t T, const mjs_o
     std::memset(&o, 0, sizeof o);
     if (out) {
       o = *out;
-      if (o.obs) o.obs += (size_t)t * N * h->obs_dim;
-      if (o.terminal_obs) o.terminal_obs += (size_t)t * N * h->obs_dim;
+      if (o.obs) o.obs += (size_t)t * N * h->inst.obs_dim;
+      if (o.terminal_obs) o.terminal_obs += (size_t)t * N * h->inst.obs_dim;
       if (o.reward) o.reward += t * N;
       if (o.discount) o.discount += t * N;
       if (o.terminated) o.terminated += t * N;
@@ -529,7 +522,7 @@ int mjs_rollout(mjs_handle* h, const double* actions_dev, int32_t T, const mjs_o
       if (o.fault) o.fault += t * N;
       if (o.ncon) o.ncon += t * N;
     }
-    int rc = launch<false>(h, make_params(h, actions_dev + (size_t)t * N * h->act_dim, nullptr, &o), (hipStream_t)stream);
+    int rc = launch<false>(h, make_params(h, actions_dev + (size_t)t * N * h->inst.act_dim, nullptr, &o), (hipStream_t)stream);
     if (rc != MJS_OK) return rc;
   }
   return MJS_OK;
@@ -592,21 +585,18 @@ int mjs_render(mjs_handle* h, int32_t camera, int32_t height, int32_t width, uin
   const bool fresh = h->prims_valid && h->prims_stream == stream;  // same state, same stream: the list is still good
   h->prims_valid = true;
   h->prims_stream = stream;
+  p.nprim = h->inst.nprim;
   if (task == MJS_TASK_POINTMASS_REACH) {
     rend::pointmass_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(p);
   } else if (task == MJS_TASK_BUTTON_PUSH) {
     if (!fresh) rend::button_prims_kernel<<<grid_for(p.N), BLOCK, 0, (hipStream_t)stream>>>(h->state, h->flags, h->prims, h->cams, p.N);
-    p.nprim = rend::BP_NPRIM;
     if (wrist) p.env_cams = h->cams;
     robot_scene();
   } else if (task == MJS_TASK_PLANAR_PUSH) {  // robot_planar_push.py:45,66: the FRONT_TILTED camera of Robot-Reach
-    const int nslots = MJS_PP_OBJECT_SLOTS(h->cfg.n_objects);
-    if (!fresh) rend::push_prims_kernel<<<grid_for(p.N), BLOCK, 0, (hipStream_t)stream>>>(h->state, h->prims, p.N, h->cfg.n_objects, nslots);
-    p.nprim = rend::ARM_NREC + 1 + nslots;
+    if (!fresh) rend::push_prims_kernel<<<grid_for(p.N), BLOCK, 0, (hipStream_t)stream>>>(h->state, h->prims, p.N, h->cfg.n_objects, p.nprim - (rend::ARM_NREC + 1));
     robot_scene();
   } else {
     if (!fresh) rend::reach_prims_kernel<<<grid_for(p.N), BLOCK, 0, (hipStream_t)stream>>>(h->state, h->prims, p.N);
-    p.nprim = rend::RR_NPRIM;
     robot_scene();
   }
   HIP_TRY(h, hipGetLastError());
@@ -642,7 +632,7 @@ int mjs_get_state(mjs_handle* h, double* state_dev, void* stream) {
   if (!h || !state_dev) return fail(h, MJS_ERR_INVALID_ARG, "mjs_get_state: null argument");
   DeviceGuard dev_(h->cfg.device);
   HIP_TRY(h, dev_.err);
-  get_state_kernel<<<grid_for(h->cfg.num_envs), BLOCK, 0, (hipStream_t)stream>>>(h->state, h->flags, state_dev, h->cfg.num_envs, h->state_dim);
+  get_state_kernel<<<grid_for(h->cfg.num_envs), BLOCK, 0, (hipStream_t)stream>>>(h->state, h->flags, state_dev, h->cfg.num_envs, h->inst.state_dim);
   HIP_TRY(h, hipGetLastError());
   return MJS_OK;
 }
@@ -652,7 +642,7 @@ int mjs_set_state(mjs_handle* h, const double* state_dev, void* stream) {
   DeviceGuard dev_(h->cfg.device);
   HIP_TRY(h, dev_.err);
   h->prims_valid = false;
-  set_state_kernel<<<grid_for(h->cfg.num_envs), BLOCK, 0, (hipStream_t)stream>>>(h->state, h->flags, state_dev, h->cfg.num_envs, h->state_dim, h->cfg.task, host_pending_byte(h));
+  set_state_kernel<<<grid_for(h->cfg.num_envs), BLOCK, 0, (hipStream_t)stream>>>(h->state, h->flags, state_dev, h->cfg.num_envs, h->inst.state_dim, h->cfg.task, host_pending_byte(h));
   HIP_TRY(h, hipGetLastError());
   return MJS_OK;
 }

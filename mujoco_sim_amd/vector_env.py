@@ -187,13 +187,7 @@ class HipVectorEnv:
         self.obs_dim = self._lib.mjs_env_obs_dim(h)  # Planar-Push: 2 block slots for n_objects <= 2, 5 for 3..5
         self.action_dim = self._lib.mjs_action_dim_for(self.spec.task_id, _ACTION_IDS.get(action_type, 0))
         self.state_dim = self._lib.mjs_env_state_dim(h)
-        self.algorithmic_bytes_per_env_step = self._lib.mjs_algorithmic_bytes_per_env_step(self.spec.task_id)
-        if task == "robot_planar_push" and self.state_dim != self._lib.mjs_state_dim(self.spec.task_id):  # 5 block slots: same formula, wider rows
-            S = (self.state_dim - 2 - 18) // 2  # rows of ONE world (the state also carries the next-episode slot, its progress row and its servo set-point)
-            self.algorithmic_bytes_per_env_step = 8 * S + 8 * (S - 3) + 2 + 8 * self.action_dim + 8 * self.obs_dim + 25
-        elif self.state_dim != self._lib.mjs_state_dim(self.spec.task_id):  # Button-Push with the articulated gripper: wider state
-            S = self.state_dim - 1
-            self.algorithmic_bytes_per_env_step = 8 * S + 8 * (S - 3) + 2 + 8 * self.action_dim + 8 * self.obs_dim + 25
+        self.algorithmic_bytes_per_env_step = self._lib.mjs_env_algorithmic_bytes_per_env_step(h)  # of the instance this handle runs
         N, dev = self.num_envs, self.device
         # every output field is a typed view into ONE device arena (64-byte aligned slots), so that a host-side consumer (the SB3
         # adapter's numpy replay buffer, scripts/sb3/reach_sac.py:93-131) needs ONE device->host copy per step for all of them

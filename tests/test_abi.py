@@ -104,3 +104,30 @@ def test_product_never_imports_oracle():
         if p.is_file() and p.suffix in {".py", ".h", ".hip", ".cpp"}:
             txt = p.read_text()
             assert "import oracle" not in txt and "from oracle" not in txt and "mjs_oracle.h" not in txt, p
+
+
+def test_integration_stub_structs_match_the_binding(native):
+    """INTEGRATION.md section 2 is the binding a reference maintainer would copy: its two ctypes structures have the size and the
+    field names, offsets and sizes of the binding this package loads the library with (mjs_create refuses any other size)."""
+    text = (ROOT / "INTEGRATION.md").read_text()
+    section = text[text.index("## 2."):text.index("## 3.")]
+    block = re.search(r"```python\n(.*?)```", section, re.S).group(1)
+    classes = block[block.index("class MjsConfig"):block.index("lib = C.CDLL")]
+    assert len(re.findall(r"^class \w+\(C\.Structure\):", classes, re.M)) == 2
+    ns = {"C": C}
+    exec(classes, ns)  # noqa: S102 - two class definitions from a document of this repository
+    for stub, ours in ((ns["MjsConfig"], native.MjsConfig), (ns["MjsOutputs"], native.MjsOutputs)):
+        assert C.sizeof(stub) == C.sizeof(ours)
+        layout = lambda s: [(n, getattr(s, n).offset, getattr(s, n).size) for n, _ in s._fields_]  # noqa: E731
+        assert layout(stub) == layout(ours)
+
+
+def test_shipped_library_reads_no_environment_knobs():
+    """The A/B knobs live in ONE block of csrc/mjsim.hip that only -DMJS_AB_KNOBS compiles; outside it the library never reads the
+    process environment (a stray variable must not change a workgroup shape)."""
+    src = (ROOT / "mujoco_sim_amd" / "csrc" / "mjsim.hip").read_text()
+    blocks = re.findall(r"^#ifdef MJS_AB_KNOBS\n.*?^#endif\n", src, re.S | re.M)
+    assert len(blocks) == 1 and len(re.findall(r"^#\s*if.*MJS_AB_KNOBS", src, re.M)) == 1
+    assert "getenv" in blocks[0]
+    outside = src.replace(blocks[0], "")
+    assert "getenv" not in outside and "<cstdlib>" not in outside

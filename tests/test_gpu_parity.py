@@ -2441,3 +2441,60 @@ def test_bench_dump_outputs_holds_the_last_timed_step(oracle_mod, tmp_path):
         o = ob.step(acts[i % 64])
     _compare(K - 1, got, o)
     assert not got["fault"].any() and not o["fault"].any()
+
+
+# The six kernel instances: (HipVectorEnv arguments, algorithmic bytes per env-step). Robot-Reach 571, Pointmass 267, Button-Push 643,
+# Planar-Push (2 block slots) 843 and Button-Push articulated 1123 are the figures the recorded profiles were collated with
+# (tools/collate_profiles.py). The 5-slot Planar-Push figure, by hand from the formula the 2-slot one follows,
+#   8 * S (one world's state rows read) + 8 * (S - 3) (written: all but the target) + 2 (flag byte r/w) + 8 * action_dim + 8 * obs_dim
+#   + 25 (reward 8, discount 8, 5 flag bytes, ncon 4)
+# with pp5's compile-time dimensions: S = 17 arm / task rows + 15 rows per block * 5 blocks = 92, action_dim = 2,
+# obs_dim = 5 + 2 * 5 = 15:  736 + 712 + 2 + 16 + 120 + 25 = 1611.
+INSTANCES = [
+    (("point_mass_reach", {}), 267),
+    (("robot_reach", {}), 571),
+    (("robot_push_button", {}), 643),
+    (("robot_push_button", {"gripper_model": "articulated"}), 1123),
+    (("robot_planar_push", {}), 843),
+    (("robot_planar_push", {"n_objects": 5}), 1611),
+]
+
+
+@pytest.mark.parametrize("args,alg_bytes", INSTANCES, ids=[a[0] + "".join(f"-{v}" for v in a[1].values()) for a, _ in INSTANCES])
+def test_per_handle_queries_of_every_instance(args, alg_bytes):
+    """What a handle reports about the instance it runs comes from the library (mjs_env_*), for all six instances; a handle of a
+    task's default instance reports what the per-task query does."""
+    import mujoco_sim_amd as m
+
+    task, kw = args
+    venv = m.HipVectorEnv(task, 4, seed=1, **kw)
+    L, h, tid = venv._lib, venv._h, venv.spec.task_id
+    assert venv.algorithmic_bytes_per_env_step == alg_bytes == L.mjs_env_algorithmic_bytes_per_env_step(h)
+    assert venv.obs_dim == L.mjs_env_obs_dim(h) and venv.state_dim == L.mjs_env_state_dim(h)
+    if not kw:
+        assert L.mjs_algorithmic_bytes_per_env_step(tid) == alg_bytes
+        assert (L.mjs_obs_dim(tid), L.mjs_state_dim(tid)) == (venv.obs_dim, venv.state_dim)
+    venv.reset()
+    assert tuple(venv.flat_obs.shape) == (4, venv.obs_dim) and tuple(venv.get_state().shape)[0] == venv.state_dim
+    venv.close()
+
+
+@pytest.mark.parametrize("N,other", [(16448, 2), (16384, 3)], ids=["above-16384-default-is-two-roles", "at-16384-default-is-reset-groups-bitwise"])
+def test_library_resolves_the_default_shape_across_16384(N, other):
+    """The library's own resolution of MJS_VARIANT_DEFAULT for Robot-Reach (an explicit kernel_variant=0, so the Python host's choice
+    is out of the way): above 16384 envs per handle it launches the two-role kernel (variant 2); up to 16384 the three-wavefront
+    kernel, whose results the reset-groups variant (3) reproduces bit for bit. 16448 = 16384 + 64 is the smallest multiple of 64
+    that takes the upper branch."""
+    import mujoco_sim_amd as m
+
+    acts = torch.from_numpy(_actions("robot_reach", 2, N)).cuda()
+    got = []
+    for variant in (0, other):
+        venv = m.HipVectorEnv("robot_reach", N, seed=31, kernel_variant=variant)
+        venv.reset()
+        for t in range(2):
+            venv.step(acts[t])
+        got.append({k: venv._buf[k].clone() for k in ("obs", "reward", "step_type", "ncon", "fault")})
+        venv.close()
+    for k in got[0]:
+        assert torch.equal(got[0][k], got[1][k]), k

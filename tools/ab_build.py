@@ -1,7 +1,10 @@
 """Diagnostic A/B builds (development tool): copy csrc/ + include/ to a scratch tree, apply textual substitutions, compile to
 ab/libmjsim_<name>.so (git-ignored, travels with gpurun). Usage:
   python tools/ab_build.py NAME [--flag=-fsome-flag ...] [--sub FILE 'old' 'new' ...]
-Load with MJS_LIB=ab/libmjsim_NAME.so (bypasses the source-hash check: never for tests or published numbers)."""
+Load with MJS_LIB=ab/libmjsim_NAME.so (bypasses the source-hash check: never for tests or published numbers).
+  --flag=-DMJS_AB_KNOBS compiles in the environment knobs of csrc/mjsim.hip (MJS_LDS_PAD, MJS_BP_EPG, MJS_BG_EPW: read once per
+  mjs_create, a value out of range is an error). The shipped library has none and never reads the process environment.
+  --flag=-DMJS_STAMPS compiles in the phase stamps and the report of csrc/mjs_stamps_report.h."""
 import shutil
 import subprocess
 import sys
