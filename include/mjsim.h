@@ -204,6 +204,31 @@ int mjs_rollout(mjs_handle* h, const double* actions_dev, int32_t T, const mjs_o
 enum { MJS_CAMERA_SCENE = 0, MJS_CAMERA_WRIST = 1 };
 int mjs_render(mjs_handle* h, int32_t camera, int32_t height, int32_t width, uint8_t* rgb_dev, void* stream);
 
+/* The scene camera of a handle (entry points added after abi 3; mjs_config and the number stay as they are). Replaces the
+ * `cameraconfig` field of RobotReachConfig / RobotPushConfig (tasks/robot_reach.py:70, robot_planar_push.py:63: any
+ * CameraConfig(position, orientation, fov), entities/camera.py:55-64) for MJS_CAMERA_SCENE of all four tasks; the Button-Push
+ * wrist camera stays mounted on the flange. The pose belongs to the handle, not to the state block: checkpoints
+ * (get / set state) neither carry nor touch it, and it plays no part in shard invariance. The camera's own body (box and lens,
+ * camera.py:78-88) moves with the pose. Collision is unchanged: neither side collides the camera's geoms,
+ * wherever the camera stands. */
+typedef struct {
+  uint32_t struct_size; /* sizeof(mjs_camera_pose), validated like mjs_config's */
+  int32_t reserved0;    /* 0 */
+  double pos[3];        /* world */
+  double quat[4];       /* MuJoCo order w,x,y,z; normalised by the library; the camera looks along its local -z, +y is up (camera.py:58) */
+  double fovy;          /* degrees, 0 < fovy < 180 */
+} mjs_camera_pose;      /* 72 bytes */
+/* pose NULL: back to the task's default. MJS_ERR_INVALID_ARG (text in mjs_last_error) for non-finite numbers, a quaternion of
+ * norm below 1e-9, fovy out of range or a wrong struct_size; the handle's camera is then unchanged. */
+int mjs_set_scene_camera(mjs_handle* h, const mjs_camera_pose* pose);
+/* the pose in use, with the quaternion normalised */
+int mjs_get_scene_camera(const mjs_handle* h, mjs_camera_pose* out);
+/* The render entry point with an optional depth map (Camera.get_depth_map, camera.py:105-114): rgb_dev uint8 [N, height, width, 3]
+ * or NULL, depth_dev float32 [N, height, width] or NULL (both NULL: MJS_ERR_INVALID_ARG). Depth is z-depth in metres, the
+ * nearest hit's distance along the optical axis as physics.render(depth=True) defines it, +inf where the ray hits nothing; the
+ * translucent Pointmass sphere counts as a surface. The rgb image is the one the rgb-only entry point above writes. */
+int mjs_render_rgbd(mjs_handle* h, int32_t camera, int32_t height, int32_t width, uint8_t* rgb_dev, float* depth_dev, void* stream);
+
 /* Test hook: the device implementation of ur5e.inverse_kinematics_closest (entities/robots/robot.py:33-37)
  * on n independent inputs: flange poses T_dev [n, 12] (row-major 3x3 rotation then translation),
  * guesses [n, 6] -> q_dev [n, 6], ok_dev [n]. No handle needed; device = current HIP device. */

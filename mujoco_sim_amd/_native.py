@@ -39,7 +39,7 @@ UR_EEF_NONE, UR_EEF_GRIPPER = 0, 1
 EXPORTED_SYMBOLS = [
     "mjs_version", "mjs_obs_dim", "mjs_action_dim", "mjs_action_dim_for", "mjs_state_dim", "mjs_env_obs_dim", "mjs_env_state_dim", "mjs_algorithmic_bytes_per_env_step", "mjs_env_algorithmic_bytes_per_env_step", "mjs_substeps",
     "mjs_create", "mjs_destroy", "mjs_last_error", "mjs_seed", "mjs_reset", "mjs_step", "mjs_rollout",
-    "mjs_get_state", "mjs_set_state", "mjs_get_rng_state", "mjs_set_rng_state", "mjs_render", "mjs_debug_ur5e_ik", "mjs_ur5e_tcp_to_joints", "mjs_ur5e_robot_run",
+    "mjs_get_state", "mjs_set_state", "mjs_get_rng_state", "mjs_set_rng_state", "mjs_render", "mjs_set_scene_camera", "mjs_get_scene_camera", "mjs_render_rgbd", "mjs_debug_ur5e_ik", "mjs_ur5e_tcp_to_joints", "mjs_ur5e_robot_run",
 ]
 
 
@@ -63,6 +63,16 @@ class MjsOutputs(C.Structure):
         ("terminated", C.c_void_p), ("truncated", C.c_void_p), ("is_success", C.c_void_p), ("step_type", C.c_void_p),
         ("fault", C.c_void_p), ("ncon", C.c_void_p),
     ]
+
+
+class MjsCameraPose(C.Structure):
+    """mjs_camera_pose: the scene camera of a handle (world position, MuJoCo quaternion w,x,y,z, vertical field of view in degrees)."""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved0", C.c_int32), ("pos", C.c_double * 3), ("quat", C.c_double * 4), ("fovy", C.c_double)]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        if "struct_size" not in kw:
+            self.struct_size = C.sizeof(MjsCameraPose)
 
 
 class MjsError(RuntimeError):
@@ -168,6 +178,9 @@ def lib() -> C.CDLL:
     L.mjs_ur5e_tcp_to_joints.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
     L.mjs_ur5e_robot_run.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
     L.mjs_render.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+    L.mjs_set_scene_camera.argtypes = [C.c_void_p, C.POINTER(MjsCameraPose)]
+    L.mjs_get_scene_camera.argtypes = [C.c_void_p, C.POINTER(MjsCameraPose)]
+    L.mjs_render_rgbd.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     L.mjs_get_rng_state.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.mjs_set_rng_state.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = L

@@ -1,4 +1,4 @@
-// mjs_render.h — fixed-camera RGB render kernels.
+// mjs_render.h — camera render kernels: RGB and z-depth.
 //
 // Replaces Camera.get_rgb_image -> physics.render(height, width, camera_id) (reference:
 // entities/camera.py:94-103; observable spec uint8 (H, W, 3), camera.py:146-150) for the scene
@@ -10,6 +10,11 @@
 //
 // Arithmetic is float32 restricted to + - * / sqrt and comparisons with FMA contraction disabled,
 // so the image is bit-identical to the independent CPU restatement in oracle/om_render.c.
+//
+// Every kernel that produces an image is a template over what it writes (OUT_RGB, OUT_DEPTH or both): depth is the
+// nearest hit's distance along the optical axis (z_depth below; Camera.get_depth_map -> physics.render(depth=True),
+// entities/camera.py:105-114), float32 [N, H, W], +inf where the ray hits nothing. The choice is made at compile time:
+// the OUT_RGB instantiations are the kernels as they were before depth existed, instruction for instruction.
 #pragma once
 #include "mjs_kernel_common.h"
 #include "mjs_pointmass.h"
@@ -35,6 +40,8 @@ struct RenderParams {
   int nprim;              // robot scenes: primitives per env
   uint8_t* out;  // [N, H, W, 3]
 };
+
+enum { OUT_RGB = 1, OUT_DEPTH = 2 };  // template argument OUT of the image kernels: what a launch writes
 
 struct F3 {
   float x, y, z;
@@ -178,6 +185,12 @@ MJS_DEV uint8_t to_u8(float c) {
   return (uint8_t)(int)(c * 255.0f + 0.5f);
 }
 
+// z-depth in metres of the hit at ray parameter t: its distance along the optical axis (the camera looks along -back)
+MJS_DEV float z_depth(float t, F3 d, const float* back) {
+  const float zs = -(d.x * back[0] + d.y * back[1] + d.z * back[2]);
+  return t < INFINITY ? t * zs : INFINITY;
+}
+
 MJS_DEV F3 pixel_ray_axes(const RenderParams& p, int row, int col, const float* right, const float* up, const float* back) {
   float aspect = (float)p.W / (float)p.H;
   float px = (2.0f * ((float)col + 0.5f) / (float)p.W - 1.0f) * p.cam.tan_half * aspect;
@@ -188,7 +201,8 @@ MJS_DEV F3 pixel_ray_axes(const RenderParams& p, int row, int col, const float* 
 MJS_DEV F3 pixel_ray(const RenderParams& p, int row, int col) { return pixel_ray_axes(p, row, col, p.cam.right, p.cam.up, p.cam.back); }
 
 // Pointmass-Reach scene: walled_pointmass_arena.xml:12-19 + pointmass sphere + target / mocap sites
-__global__ __launch_bounds__(256) void pointmass_kernel(RenderParams p) {
+template <int OUT>
+__global__ __launch_bounds__(256) void pointmass_kernel(RenderParams p, float* depth) {
   const int env = blockIdx.y;
   const int pix = blockIdx.x * 256 + threadIdx.x;
   if (pix >= p.H * p.W) return;
@@ -213,13 +227,16 @@ __global__ __launch_bounds__(256) void pointmass_kernel(RenderParams p) {
   hit_aabb(eye, d, f3(tx, ty, (float)(MJS_PM_RADIUS / 2)), MJS_PM_TARGET_HALF, f3(MJS_PM_TARGET_RGB[0], MJS_PM_TARGET_RGB[1], MJS_PM_TARGET_RGB[2]), s);
   hit_sphere(eye, d, f3(mx, my, 0.0f), MJS_PM_MOCAP_SITE_RADIUS, f3(MJS_SITE_DEFAULT_RGB[0], MJS_SITE_DEFAULT_RGB[1], MJS_SITE_DEFAULT_RGB[2]), s);
   F3 c = f3(0, 0, 0);  // background
-  if (s.t < INFINITY) c = shade<2>(add(eye, mul(s.t, d)), s.n, eye, s.rgb, MJS_PM_LIGHT_POS);
+  if ((OUT & OUT_RGB) && s.t < INFINITY) c = shade<2>(add(eye, mul(s.t, d)), s.n, eye, s.rgb, MJS_PM_LIGHT_POS);
   // translucent pointmass sphere blended over whatever is behind it
   Surf b;
   b.t = s.t;
   b.n = f3(0, 0, 1);
   b.rgb = f3(0, 0, 0);
   hit_sphere(eye, d, f3(qx, qy, (float)MJS_PM_RADIUS), (float)MJS_PM_RADIUS, f3(MJS_PM_SPHERE_RGBA[0], MJS_PM_SPHERE_RGBA[1], MJS_PM_SPHERE_RGBA[2]), b);
+  // the translucent sphere counts as a surface: depth is the nearest of it and what lies behind it (b.t <= s.t)
+  if (OUT & OUT_DEPTH) depth[(size_t)env * p.H * p.W + pix] = z_depth(b.t, d, p.cam.back);
+  if (!(OUT & OUT_RGB)) return;
   if (b.t < s.t) {
     F3 sc = shade<2>(add(eye, mul(b.t, d)), b.n, eye, b.rgb, MJS_PM_LIGHT_POS);
     const float a = MJS_PM_SPHERE_RGBA[3];
@@ -296,10 +313,14 @@ MJS_DEV void camera_body_prims(V3 pos, V3 ax, V3 ay, float* box, float* lens) {
 }
 
 // Button-Push scene (robot_push_button.py:66-96): arm + stand-ins, wrist camera body, scene camera body,
-// switch box and button. Also writes the wrist camera pose of every env (cams [N][12]).
+// switch box and button. Also writes the wrist camera pose of every env (cams [N][12]). The scene camera's body stands where
+// the handle's scene camera is (ScenePose: the task's default, or what mjs_set_scene_camera gave).
+struct ScenePose {
+  double pos[3], quat[4];
+};
 constexpr int BP_NPRIM = ARM_NREC + 2 + 2 + 2;  // arm, wrist camera body, scene camera body, switch box + button
 static_assert(BP_NPRIM <= MAX_NPRIM && RR_NPRIM <= MAX_NPRIM, "one candidate bit per primitive");
-__global__ __launch_bounds__(64) void button_prims_kernel(const double* state, const uint8_t* flags, float* prims, float* cams, int N) {
+__global__ __launch_bounds__(64) void button_prims_kernel(const double* state, const uint8_t* flags, float* prims, float* cams, int N, ScenePose scene) {
   const int i = blockIdx.x * 64 + threadIdx.x;
   if (i >= N) return;
   double q[6];
@@ -324,8 +345,8 @@ __global__ __launch_bounds__(64) void button_prims_kernel(const double* state, c
   put3(cm, wpos); put3(cm + 3, wright); put3(cm + 6, wup); put3(cm + 9, wback);
   {  // scene camera body (seen by the wrist camera only)
     double Rs[9];
-    quat_to_mat(MJS_BP_CAM_QUAT, Rs);
-    camera_body_prims(v3(MJS_BP_CAM_POS[0], MJS_BP_CAM_POS[1], MJS_BP_CAM_POS[2]), v3(Rs[0], Rs[3], Rs[6]), v3(Rs[1], Rs[4], Rs[7]),
+    quat_to_mat(scene.quat, Rs);
+    camera_body_prims(v3(scene.pos[0], scene.pos[1], scene.pos[2]), v3(Rs[0], Rs[3], Rs[6]), v3(Rs[1], Rs[4], Rs[7]),
                       out + (ARM_NREC + 2) * PRIM_FLOATS, out + (ARM_NREC + 3) * PRIM_FLOATS);
   }
   const V3 sw = v3(state[(size_t)(bp::S_SWITCH + 0) * N + i], state[(size_t)(bp::S_SWITCH + 1) * N + i], state[(size_t)(bp::S_SWITCH + 2) * N + i]);
@@ -555,7 +576,8 @@ MJS_DEV bool eye_inside(const float* pr, F3 eye) {
 // workgroup; lane k of every wavefront tests primitive k against the cone that bounds the tile's 64 rays, and the
 // ballot of that test is the list of primitives the wavefront walks (typically 0-3 of ~20). All of this only
 // SKIPS exact tests that cannot hit: the image is unchanged.
-__global__ __launch_bounds__(256) void robot_scene_kernel(RenderParams p, const float* prims) {
+template <int OUT>
+__global__ __launch_bounds__(256) void robot_scene_kernel(RenderParams p, const float* prims, float* depth) {
   __shared__ float lds_prims[MAX_NPRIM * PRIM_FLOATS];
   const int env = blockIdx.y;
   const int nprim = p.nprim;
@@ -634,6 +656,8 @@ __global__ __launch_bounds__(256) void robot_scene_kernel(RenderParams p, const 
     else hit_obb(eye, d, p0, p1, f3(pr[7], pr[8], pr[9]), f3(pr[10], pr[11], pr[12]), rgb, s);
   }
   if (!inside) return;
+  if (OUT & OUT_DEPTH) depth[(size_t)env * p.H * p.W + (size_t)row * p.W + col] = z_depth(s.t, d, back);
+  if (!(OUT & OUT_RGB)) return;
   F3 c = f3(0, 0, 0);
   if (s.t < INFINITY)  // body-mounted camera: the fast normalisation, as the rectangle walk (normalize_fast)
     c = p.env_cams ? shade<6, true>(add(eye, mul(s.t, d)), s.n, eye, s.rgb, MJS_RR_LIGHT_POS) : shade<6>(add(eye, mul(s.t, d)), s.n, eye, s.rgb, MJS_RR_LIGHT_POS);
@@ -661,6 +685,14 @@ __global__ __launch_bounds__(256) void robot_scene_kernel(RenderParams p, const 
 // rectangle touches are visited and only pixels a primitive wins are shaded; the rest is a copy of the table.
 // Same arithmetic per ray, per test and per shaded pixel as the tile kernel, evaluated by the same functions: the image
 // is identical (tests: test_scene_camera_kernels_agree_byte_for_byte, both cameras, varied poses).
+//
+// Depth (OUT_DEPTH) is NOT staged: a wavefront stores its tile's 64 depths straight from registers, eight 32-byte runs of
+// whole dwords per store instruction, which the L2 merges with the neighbouring tiles' runs before the lines leave for HBM.
+// The workgroup already holds 25.6 KB of LDS (21.5 KB with the table), i.e. six (seven) workgroups per CU of 160 KB; a
+// second 16 KB array would leave three (four), and the walk - LDS reads and divergent exact tests - lives on the other
+// wavefronts' work while one waits. The colours stay packed in their 16 KB because three bytes per pixel cannot be
+// stored as dwords from a tile's lanes. With a table, tiles no primitive touches are not skipped when depth is written:
+// their depth comes from the floor's ray parameter in ray.w.
 constexpr int RECT_WALK_MAX_PIXELS = 64 * 64;  // 16 KB of packed colours in LDS
 struct Background {
   const float4* ray;    // [H*W] normalised ray direction (xyz) and the floor's ray parameter (w; +inf = no floor there)
@@ -937,11 +969,11 @@ MJS_DEV void prim_rect(const RenderParams& p, const float* pr, F3 eye, const flo
   rect[0] = r0; rect[1] = r1; rect[2] = c0; rect[3] = c1;
 }
 
-template <bool FIXED>  // FIXED: the task's scene camera with its ray / floor table (Background); otherwise p.env_cams
-__global__ __launch_bounds__(256) void robot_scene_rect_walk_kernel(RenderParams p, const float* prims, Background bg, int band_rows) {
+template <bool FIXED, int OUT>  // FIXED: the task's scene camera with its ray / floor table (Background); otherwise p.env_cams
+__global__ __launch_bounds__(256) void robot_scene_rect_walk_kernel(RenderParams p, const float* prims, Background bg, int band_rows, float* depth) {
   __shared__ float lds_prims[MAX_NPRIM * PRIM_FLOATS];
   __shared__ int bbox[MAX_NPRIM * 4];
-  __shared__ uint32_t image[RECT_WALK_MAX_PIXELS];  // packed colours, written out coalesced at the end
+  __shared__ uint32_t image[(OUT & OUT_RGB) ? RECT_WALK_MAX_PIXELS : 1];  // packed colours, written out coalesced at the end
   __shared__ int next_tile;                        // tiles are taken in turn by whichever wavefront is free
   // body-mounted camera: the image-plane coordinates of a column / a row (pixel_ray_axes' px, py: two IEEE divisions per
   // pixel) are the same for every pixel of that column / row: computed once per workgroup with the same expressions, read
@@ -961,9 +993,10 @@ __global__ __launch_bounds__(256) void robot_scene_rect_walk_kernel(RenderParams
     const float* pe = prims + (size_t)env * nprim * PRIM_FLOATS;
     for (int k = tid; k < nprim * PRIM_FLOATS; k += 256) lds_prims[k] = pe[k];
     if (tid == 0) next_tile = 0;
-    if (FIXED)  // the env-independent image first; only tiles a primitive touches are revisited
-      for (int k = tid; k < npix; k += 256) image[k] = bg.rgb[pix0 + k];
-    else {
+    if (FIXED) {  // the env-independent image first; only tiles a primitive touches are revisited
+      if (OUT & OUT_RGB)
+        for (int k = tid; k < npix; k += 256) image[k] = bg.rgb[pix0 + k];
+    } else {
       const float aspect = (float)p.W / (float)p.H;
       for (int col = tid; col < p.W; col += 256) pxtab[col] = (2.0f * ((float)col + 0.5f) / (float)p.W - 1.0f) * p.cam.tan_half * aspect;
       for (int r = tid; r < rows; r += 256) pytab[r] = (1.0f - 2.0f * ((float)(band0 + r) + 0.5f) / (float)p.H) * p.cam.tan_half;
@@ -1021,7 +1054,7 @@ __global__ __launch_bounds__(256) void robot_scene_rect_walk_kernel(RenderParams
     s.rgb = f3(0, 0, 0);
     float t_floor = INFINITY;
     if (FIXED) {  // the env-independent part comes from the table: a tile no primitive touches is a copy
-      if (!cand) continue;
+      if (!(OUT & OUT_DEPTH) && !cand) continue;
       const float4 r4 = bg.ray[row * p.W + col];
       d = f3(r4.x, r4.y, r4.z);
       t_floor = r4.w;
@@ -1041,6 +1074,8 @@ __global__ __launch_bounds__(256) void robot_scene_rect_walk_kernel(RenderParams
       if (along - br > s.t) continue;  // every point of the bound lies beyond the nearest hit so far: it cannot pass the strict-< update
       exact_test_pre(pr, pconst[k], eye, d, s);
     }
+    if (OUT & OUT_DEPTH) depth[(size_t)env * p.H * p.W + (size_t)row * p.W + col] = z_depth(s.t, d, back);
+    if (!(OUT & OUT_RGB)) continue;
     if (FIXED) {
       if (s.t < t_floor) image[(row - band0) * p.W + col] = pack_rgb(shade<6>(add(eye, mul(s.t, d)), s.n, eye, s.rgb, MJS_RR_LIGHT_POS));  // a primitive won the pixel
     } else {
@@ -1049,6 +1084,7 @@ __global__ __launch_bounds__(256) void robot_scene_rect_walk_kernel(RenderParams
       image[(row - band0) * p.W + col] = pack_rgb(cc);
     }
   }
+  if (!(OUT & OUT_RGB)) return;
   __syncthreads();
   uint32_t* o32 = reinterpret_cast<uint32_t*>(p.out + ((size_t)env * p.H * p.W + pix0) * 3);  // pix0 * 3 bytes: a multiple of 4 (W % 8 == 0)
   for (int q = tid; q < (npix >> 2); q += 256) {

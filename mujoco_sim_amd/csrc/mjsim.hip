@@ -103,9 +103,12 @@ struct mjs_handle {
   int32_t* rng_pos = nullptr;  // [N]
   unsigned long long* stamps = nullptr;  // diagnostic builds only
   float* prims = nullptr;      // [N][nprim][PRIM_FLOATS] render primitive list (robot scenes)
-  float4* bg_ray = nullptr;    // [bg_H * bg_W] scene-camera ray table (rend::Background), built at the first render of a size
+  float4* bg_ray = nullptr;    // [bg_H * bg_W] scene-camera ray table (rend::Background), built at the first render of a size and pose
   uint32_t* bg_rgb = nullptr;
   int bg_H = 0, bg_W = 0;
+  unsigned bg_serial = 0;      // the cam_serial the table was built for
+  mjs_camera_pose cam;         // the scene camera: the task's default, or what mjs_set_scene_camera gave (not part of the state block)
+  unsigned cam_serial = 0;     // counts mjs_set_scene_camera calls
   float* cams = nullptr;       // [N][12] wrist-camera poses (Button-Push)
   double* ws = nullptr;        // [rr::WS_ROWS][N] contact workspace of the general constraint stage (Robot-Reach, Button-Push)
   int epoch = 0;               // parity of the next step launch (FLAG_EPOCH)
@@ -355,6 +358,56 @@ int launch(mjs_handle* h, const KernelParams& p, hipStream_t s) {
   return MJS_OK;
 }
 
+void default_scene_camera(int task, mjs_camera_pose& c) {
+  const double* q = task == MJS_TASK_POINTMASS_REACH ? MJS_PM_CAM_QUAT : task == MJS_TASK_BUTTON_PUSH ? MJS_BP_CAM_QUAT : MJS_RR_CAM_QUAT;
+  const double* cpos = task == MJS_TASK_POINTMASS_REACH ? MJS_PM_CAM_POS : task == MJS_TASK_BUTTON_PUSH ? MJS_BP_CAM_POS : MJS_RR_CAM_POS;
+  c.struct_size = (uint32_t)sizeof(mjs_camera_pose);
+  c.reserved0 = 0;
+  for (int k = 0; k < 3; k++) c.pos[k] = cpos[k];
+  for (int k = 0; k < 4; k++) c.quat[k] = q[k];
+  c.fovy = task == MJS_TASK_POINTMASS_REACH ? MJS_PM_CAM_FOVY : task == MJS_TASK_BUTTON_PUSH ? MJS_BP_CAM_FOVY : MJS_RR_CAM_FOVY;
+}
+
+// The launches of one render, for what it writes (OUT: rend::OUT_RGB | rend::OUT_DEPTH). The OUT_RGB instantiations are the
+// kernels mjs_render has always launched.
+template <int OUT>
+int render_launch(mjs_handle* h, rend::RenderParams& p, float* depth, bool wrist, bool rect_walk, int band_rows, unsigned nbands, hipStream_t stream) {
+  const int task = h->cfg.task, height = p.H, width = p.W;
+  dim3 grid((unsigned)((height * width + 255) / 256), (unsigned)p.N);
+  const int tiles = ((height + 7) / 8) * ((width + 7) / 8);  // robot scenes: one wavefront per 8x8 tile
+  dim3 tile_grid((unsigned)((tiles + 3) / 4), (unsigned)p.N);
+  auto robot_scene = [&]() {
+    const dim3 rw_grid((unsigned)p.N, nbands);
+    if (rect_walk && p.env_cams) rend::robot_scene_rect_walk_kernel<false, OUT><<<rw_grid, 256, 0, stream>>>(p, h->prims, rend::Background{nullptr, nullptr}, band_rows, depth);
+    else if (rect_walk) rend::robot_scene_rect_walk_kernel<true, OUT><<<rw_grid, 256, 0, stream>>>(p, h->prims, rend::Background{h->bg_ray, h->bg_rgb}, band_rows, depth);
+    else rend::robot_scene_kernel<OUT><<<tile_grid, 256, 0, stream>>>(p, h->prims, depth);
+  };
+  const bool fresh = h->prims_valid && h->prims_stream == stream;  // same state, same stream: the list is still good
+  h->prims_valid = true;
+  h->prims_stream = stream;
+  p.nprim = h->inst.nprim;
+  if (task == MJS_TASK_POINTMASS_REACH) {
+    rend::pointmass_kernel<OUT><<<grid, 256, 0, stream>>>(p, depth);
+  } else if (task == MJS_TASK_BUTTON_PUSH) {
+    if (!fresh) {
+      rend::ScenePose sp;
+      for (int k = 0; k < 3; k++) sp.pos[k] = h->cam.pos[k];
+      for (int k = 0; k < 4; k++) sp.quat[k] = h->cam.quat[k];
+      rend::button_prims_kernel<<<grid_for(p.N), BLOCK, 0, stream>>>(h->state, h->flags, h->prims, h->cams, p.N, sp);
+    }
+    if (wrist) p.env_cams = h->cams;
+    robot_scene();
+  } else if (task == MJS_TASK_PLANAR_PUSH) {  // robot_planar_push.py:45,66: the FRONT_TILTED camera of Robot-Reach unless the handle's was set
+    if (!fresh) rend::push_prims_kernel<<<grid_for(p.N), BLOCK, 0, stream>>>(h->state, h->prims, p.N, h->cfg.n_objects, p.nprim - (rend::ARM_NREC + 1));
+    robot_scene();
+  } else {
+    if (!fresh) rend::reach_prims_kernel<<<grid_for(p.N), BLOCK, 0, stream>>>(h->state, h->prims, p.N);
+    robot_scene();
+  }
+  HIP_TRY(h, hipGetLastError());
+  return MJS_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -417,6 +470,7 @@ int mjs_create(const mjs_config* cfg, mjs_handle** out) {
   if (h->cfg.max_episode_steps <= 0) h->cfg.max_episode_steps = MJS_PP_MAX_CONTROL_STEPS;
   if (!(h->cfg.time_limit > 0)) h->cfg.time_limit = default_time_limit(cfg->task);
   h->inst = resolve_instance(h->cfg);
+  default_scene_camera(cfg->task, h->cam);
   const Instance& in = h->inst;
   const size_t N = (size_t)cfg->num_envs;
   CREATE_TRY("device allocation", dev_.err);
@@ -528,8 +582,42 @@ int mjs_rollout(mjs_handle* h, const double* actions_dev, int32_t T, const mjs_o
   return MJS_OK;
 }
 
-int mjs_render(mjs_handle* h, int32_t camera, int32_t height, int32_t width, uint8_t* rgb_dev, void* stream) {
-  if (!h || !rgb_dev) return fail(h, MJS_ERR_INVALID_ARG, "mjs_render: null argument");
+// ---- cameras ------------------------------------------------------------------------------------------------------------
+int mjs_set_scene_camera(mjs_handle* h, const mjs_camera_pose* pose) {
+  if (!h) return fail(nullptr, MJS_ERR_INVALID_ARG, "mjs_set_scene_camera: null handle");
+  mjs_camera_pose c;
+  if (!pose) default_scene_camera(h->cfg.task, c);
+  else {
+    if (pose->struct_size != sizeof(mjs_camera_pose))
+      return fail(h, MJS_ERR_INVALID_ARG, "mjs_set_scene_camera: mjs_camera_pose.struct_size does not match this library's header");
+    c = *pose;
+    bool finite = std::isfinite(c.fovy);
+    double n2 = 0;
+    for (int k = 0; k < 3; k++) finite = finite && std::isfinite(c.pos[k]);
+    for (int k = 0; k < 4; k++) { finite = finite && std::isfinite(c.quat[k]); n2 += c.quat[k] * c.quat[k]; }
+    if (!finite) return fail(h, MJS_ERR_INVALID_ARG, "mjs_set_scene_camera: position, quaternion and fovy must be finite");
+    if (!(std::sqrt(n2) >= 1e-9)) return fail(h, MJS_ERR_INVALID_ARG, "mjs_set_scene_camera: the quaternion's norm is below 1e-9");
+    if (!(c.fovy > 0 && c.fovy < 180)) return fail(h, MJS_ERR_INVALID_ARG, "mjs_set_scene_camera: fovy must lie in (0, 180) degrees");
+  }
+  // kept as given: the frame is derived from these numbers exactly as from the compiled-in defaults (a pose equal to the default
+  // gives the default's images byte for byte); mjs_get_scene_camera normalises the quaternion
+  h->cam = c;
+  h->cam_serial++;         // the ray / floor table of the old pose is void ...
+  h->prims_valid = false;  // ... and so is the primitive list: the camera's own body moves with the pose
+  return MJS_OK;
+}
+
+int mjs_get_scene_camera(const mjs_handle* h, mjs_camera_pose* out) {
+  if (!h || !out) return fail(nullptr, MJS_ERR_INVALID_ARG, "mjs_get_scene_camera: null argument");
+  *out = h->cam;
+  const double* q = h->cam.quat;
+  const double n = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+  for (int k = 0; k < 4; k++) out->quat[k] = q[k] / n;
+  return MJS_OK;
+}
+
+int mjs_render_rgbd(mjs_handle* h, int32_t camera, int32_t height, int32_t width, uint8_t* rgb_dev, float* depth_dev, void* stream) {
+  if (!h || (!rgb_dev && !depth_dev)) return fail(h, MJS_ERR_INVALID_ARG, "mjs_render_rgbd: null handle, or neither an rgb nor a depth buffer");
   const int task = h->cfg.task;
   const bool wrist = camera == MJS_CAMERA_WRIST;
   if ((camera != MJS_CAMERA_SCENE && !(wrist && task == MJS_TASK_BUTTON_PUSH)) || height <= 0 || width <= 0)
@@ -540,9 +628,9 @@ int mjs_render(mjs_handle* h, int32_t camera, int32_t height, int32_t width, uin
   p.N = h->cfg.num_envs; p.H = height; p.W = width; p.state = h->state; p.out = rgb_dev;
   p.env_cams = nullptr; p.nprim = 0;
   // camera frame from the MuJoCo quaternion (w,x,y,z): columns of R are the local x (right), y (up), z (back) axes
-  const double* q = task == MJS_TASK_POINTMASS_REACH ? MJS_PM_CAM_QUAT : task == MJS_TASK_BUTTON_PUSH ? MJS_BP_CAM_QUAT : MJS_RR_CAM_QUAT;
-  const double* cpos = task == MJS_TASK_POINTMASS_REACH ? MJS_PM_CAM_POS : task == MJS_TASK_BUTTON_PUSH ? MJS_BP_CAM_POS : MJS_RR_CAM_POS;
-  const double fovy = wrist ? MJS_WCAM_FOVY : task == MJS_TASK_POINTMASS_REACH ? MJS_PM_CAM_FOVY : task == MJS_TASK_BUTTON_PUSH ? MJS_BP_CAM_FOVY : MJS_RR_CAM_FOVY;
+  const double* q = h->cam.quat;
+  const double* cpos = h->cam.pos;
+  const double fovy = wrist ? MJS_WCAM_FOVY : h->cam.fovy;
   const double n = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
   const double w = q[0] / n, x = q[1] / n, y = q[2] / n, z = q[3] / n;
   const double R[9] = {1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w), 2 * (x * y + z * w), 1 - 2 * (x * x + z * z),
@@ -554,18 +642,16 @@ int mjs_render(mjs_handle* h, int32_t camera, int32_t height, int32_t width, uin
     p.cam.back[k] = (float)R[3 * k + 2];
   }
   p.cam.tan_half = (float)std::tan(fovy * 3.14159265358979323846 / 360.0);
-  dim3 grid((unsigned)((height * width + 255) / 256), (unsigned)p.N);
-  const int tiles = ((height + 7) / 8) * ((width + 7) / 8);  // robot scenes: one wavefront per 8x8 tile
-  dim3 tile_grid((unsigned)((tiles + 3) / 4), (unsigned)p.N);
   // robot scenes: the rectangle walk (per-primitive pixel rectangles, colours staged in 16 KB of LDS) with one workgroup per
   // env image, or per band of rows when the image has more than 4096 pixels; the fixed scene cameras add the table of
-  // env-independent rays and floor colours, computed once per size. Sizes that are not multiples of 8 (and kernel_variant 1)
-  // keep the 8x8-tile walk. Ladder: profiles/r02_g_render_ladder.txt.
+  // env-independent rays and floor colours, computed once per size and pose. Sizes that are not multiples of 8 (and
+  // kernel_variant 1) keep the 8x8-tile walk. Ladder: profiles/r02_g_render_ladder.txt.
   int band_rows = height;
   if (height * width > rend::RECT_WALK_MAX_PIXELS) band_rows = (rend::RECT_WALK_MAX_PIXELS / width) & ~7;
   const bool rect_walk = height % 8 == 0 && width % 8 == 0 && band_rows >= 8 && h->cfg.kernel_variant != MJS_VARIANT_SINGLE_WAVE;
   const unsigned nbands = rect_walk ? (unsigned)((height + band_rows - 1) / band_rows) : 1u;
-  if (rect_walk && !wrist && (h->bg_H != height || h->bg_W != width)) {  // the scene camera of a handle never moves: keyed by size only
+  // the table is keyed by the image size and by the pose it was built for (cam_serial counts mjs_set_scene_camera calls)
+  if (rect_walk && !wrist && (h->bg_H != height || h->bg_W != width || h->bg_serial != h->cam_serial)) {
     if (h->bg_ray) (void)hipFree(h->bg_ray);
     if (h->bg_rgb) (void)hipFree(h->bg_rgb);
     h->bg_ray = nullptr; h->bg_rgb = nullptr; h->bg_H = h->bg_W = 0;
@@ -573,34 +659,17 @@ int mjs_render(mjs_handle* h, int32_t camera, int32_t height, int32_t width, uin
     HIP_TRY(h, hipMalloc(&h->bg_rgb, sizeof(uint32_t) * height * width));
     rend::scene_background_kernel<<<(unsigned)((height * width + 255) / 256), 256, 0, (hipStream_t)stream>>>(p, h->bg_ray, h->bg_rgb);
     HIP_TRY(h, hipGetLastError());
-    HIP_TRY(h, hipStreamSynchronize((hipStream_t)stream));  // once per size: later renders may come on another stream
-    h->bg_H = height; h->bg_W = width;
+    HIP_TRY(h, hipStreamSynchronize((hipStream_t)stream));  // once per size and pose: later renders may come on another stream
+    h->bg_H = height; h->bg_W = width; h->bg_serial = h->cam_serial;
   }
-  auto robot_scene = [&]() {
-    const dim3 rw_grid((unsigned)p.N, nbands);
-    if (rect_walk && p.env_cams) rend::robot_scene_rect_walk_kernel<false><<<rw_grid, 256, 0, (hipStream_t)stream>>>(p, h->prims, rend::Background{nullptr, nullptr}, band_rows);
-    else if (rect_walk) rend::robot_scene_rect_walk_kernel<true><<<rw_grid, 256, 0, (hipStream_t)stream>>>(p, h->prims, rend::Background{h->bg_ray, h->bg_rgb}, band_rows);
-    else rend::robot_scene_kernel<<<tile_grid, 256, 0, (hipStream_t)stream>>>(p, h->prims);
-  };
-  const bool fresh = h->prims_valid && h->prims_stream == stream;  // same state, same stream: the list is still good
-  h->prims_valid = true;
-  h->prims_stream = stream;
-  p.nprim = h->inst.nprim;
-  if (task == MJS_TASK_POINTMASS_REACH) {
-    rend::pointmass_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(p);
-  } else if (task == MJS_TASK_BUTTON_PUSH) {
-    if (!fresh) rend::button_prims_kernel<<<grid_for(p.N), BLOCK, 0, (hipStream_t)stream>>>(h->state, h->flags, h->prims, h->cams, p.N);
-    if (wrist) p.env_cams = h->cams;
-    robot_scene();
-  } else if (task == MJS_TASK_PLANAR_PUSH) {  // robot_planar_push.py:45,66: the FRONT_TILTED camera of Robot-Reach
-    if (!fresh) rend::push_prims_kernel<<<grid_for(p.N), BLOCK, 0, (hipStream_t)stream>>>(h->state, h->prims, p.N, h->cfg.n_objects, p.nprim - (rend::ARM_NREC + 1));
-    robot_scene();
-  } else {
-    if (!fresh) rend::reach_prims_kernel<<<grid_for(p.N), BLOCK, 0, (hipStream_t)stream>>>(h->state, h->prims, p.N);
-    robot_scene();
-  }
-  HIP_TRY(h, hipGetLastError());
-  return MJS_OK;
+  if (rgb_dev && depth_dev) return render_launch<rend::OUT_RGB | rend::OUT_DEPTH>(h, p, depth_dev, wrist, rect_walk, band_rows, nbands, (hipStream_t)stream);
+  if (depth_dev) return render_launch<rend::OUT_DEPTH>(h, p, depth_dev, wrist, rect_walk, band_rows, nbands, (hipStream_t)stream);
+  return render_launch<rend::OUT_RGB>(h, p, nullptr, wrist, rect_walk, band_rows, nbands, (hipStream_t)stream);
+}
+
+int mjs_render(mjs_handle* h, int32_t camera, int32_t height, int32_t width, uint8_t* rgb_dev, void* stream) {
+  if (!h || !rgb_dev) return fail(h, MJS_ERR_INVALID_ARG, "mjs_render: null argument");
+  return mjs_render_rgbd(h, camera, height, width, rgb_dev, nullptr, stream);
 }
 
 int mjs_debug_ur5e_ik(const double* T_dev, const double* guess_dev, double* q_dev, uint8_t* ok_dev, int32_t n, void* stream) {

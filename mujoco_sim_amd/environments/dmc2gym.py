@@ -61,6 +61,8 @@ class HipEnvironment:
             kwargs["action_type"] = task.action_type
             kwargs["button_disturbances"] = task.button_disturbances
             kwargs["use_wrist_camera"] = task.use_wrist_camera
+        if getattr(task, "cameraconfig", None) is not None:  # Robot-Reach / Planar-Push: the config's scene camera
+            kwargs["cameraconfig"] = task.cameraconfig
         self._venv = HipVectorEnv(task.task_name, 1, device=device, autoreset="next_step", reward_type=task.reward_type,
                                   time_limit=(1e300 if np.isinf(time_limit) else time_limit),
                                   observation_type=getattr(task, "observation_type", STATE_OBS),

@@ -11,6 +11,7 @@ import dataclasses
 
 import numpy as np
 
+from ...entities.camera import CameraConfig
 from .point_reach import BoundedArraySpec
 
 
@@ -22,6 +23,8 @@ class RobotPushConfig:
     VISUAL_OBS = "visual_observations"
     REWARD_TYPES = (SPARSE_REWARD, DENSE_NEG_DISTANCE_REWARD)
     OBSERVATION_TYPES = (STATE_OBS, VISUAL_OBS)
+    TOP_DOWN_CAMERA_CONFIG = CameraConfig(np.array([0.0, -0.5, 2.4]), np.array([1.0, 0.0, 0.0, 0.0]), 30)  # robot_planar_push.py:42-43
+    FRONT_TILTED_CAMERA_CONFIG = CameraConfig(np.array([0.0, -1.1, 0.5]), np.array([-0.7, -0.35, 0, 0.0]), 70)
 
     reward_type: str = None
     observation_type: str = None
@@ -34,10 +37,12 @@ class RobotPushConfig:
     nearest_object_reward_coefficient: float = 0.1
     target_radius = 0.05
     n_objects: int = 5  # robot_planar_push.py:61; 1..2 run the 2-slot kernel, 3..5 the 5-slot kernel
+    cameraconfig: CameraConfig = None  # the scene camera (robot_planar_push.py:63,70): None = FRONT_TILTED_CAMERA_CONFIG
 
     def __post_init__(self):
         self.reward_type = self.reward_type or RobotPushConfig.DENSE_NEG_DISTANCE_REWARD
         self.observation_type = self.observation_type or RobotPushConfig.STATE_OBS
+        self.cameraconfig = self.cameraconfig or RobotPushConfig.FRONT_TILTED_CAMERA_CONFIG
         assert self.observation_type in RobotPushConfig.OBSERVATION_TYPES
         assert self.reward_type in RobotPushConfig.REWARD_TYPES
         if not 1 <= self.n_objects <= 5:
@@ -56,6 +61,9 @@ class RobotPushTask:
         self.reward_type = self.config.reward_type
         self.observation_type = self.config.observation_type
         self.image_resolution = self.config.image_resolution
+        # robot_planar_push.py:110-111: the task overwrites the camera config's image size with its image_resolution
+        self.cameraconfig = self.config.cameraconfig
+        self.cameraconfig.image_width = self.cameraconfig.image_height = self.config.image_resolution
 
     @property
     def CONTROL_TIMESTEP(self):

@@ -10,6 +10,7 @@ import dataclasses
 
 import numpy as np
 
+from ...entities.camera import CameraConfig
 from .point_reach import BoundedArraySpec
 
 
@@ -26,6 +27,7 @@ class RobotReachConfig:
     REWARD_TYPES = (SPARSE_REWARD, DENSE_NEG_DISTANCE_REWARD)
     OBSERVATION_TYPES = (STATE_OBS, VISUAL_OBS)
     ACTION_TYPES = (REL_EEF_ACTION, ABS_EEF_ACTION, REL_JOIN_ACTION, ABS_JOIN_ACTION)
+    FRONT_TILTED_CAMERA_CONFIG = CameraConfig(np.array([0.0, -1.1, 0.5]), np.array([-0.7, -0.35, 0, 0.0]), 70)  # robot_reach.py:52
 
     reward_type: str = None
     observation_type: str = None
@@ -39,11 +41,13 @@ class RobotReachConfig:
     target_radius = 0.03
     # opt-in: the reference task never terminates on success
     terminate_on_success: bool = False
+    cameraconfig: CameraConfig = None  # the scene camera (robot_reach.py:70,78): None = FRONT_TILTED_CAMERA_CONFIG
 
     def __post_init__(self):
         self.reward_type = self.reward_type or RobotReachConfig.DENSE_NEG_DISTANCE_REWARD
         self.observation_type = self.observation_type or RobotReachConfig.STATE_OBS
         self.action_type = self.action_type or RobotReachConfig.ABS_EEF_ACTION
+        self.cameraconfig = self.cameraconfig or RobotReachConfig.FRONT_TILTED_CAMERA_CONFIG
         assert self.observation_type in RobotReachConfig.OBSERVATION_TYPES
         assert self.reward_type in RobotReachConfig.REWARD_TYPES
         assert self.action_type in RobotReachConfig.ACTION_TYPES
@@ -59,6 +63,9 @@ class RobotReachTask:
         self.reward_type = self.config.reward_type
         self.observation_type = self.config.observation_type
         self.image_resolution = self.config.image_resolution
+        # robot_reach.py:116-117: the task overwrites the camera config's image size with its image_resolution
+        self.cameraconfig = self.config.cameraconfig
+        self.cameraconfig.image_width = self.cameraconfig.image_height = self.config.image_resolution
         if self.config.action_type != RobotReachConfig.ABS_EEF_ACTION:
             # the reference's before_step only implements the absolute-EEF path (robot_reach.py:159-169)
             raise NotImplementedError("only ABS_EEF_ACTION is implemented (as in the reference)")

@@ -96,13 +96,15 @@ def _as_uint8_ptr(t):
 _RAW_STREAM = getattr(torch._C, "_cuda_getCurrentRawStream", None)
 
 
-def visual_observation_layout(task: str, action_type: str | None = None, image_resolution: int = 64, use_wrist_camera: bool = True):
+def visual_observation_layout(task: str, action_type: str | None = None, image_resolution: int = 64, use_wrist_camera: bool = True,
+                              depth_observations: bool = False):
     """Keys, shapes and dtypes of a task's VISUAL observation dict in the reference's order (host logic, no device needed):
     proprioception + camera image(s) - point_reach.py:119-121, robot_reach.py:139-141, robot_push_button.py:113-124; dict order =
     composer's entity order (robot, wrist camera on the robot, scene camera). The wrist camera's key is what the reference's code
     produces at HEAD, ``ur5e/Camera/rgb_image`` (setting ``observable.name`` at robot_push_button.py:95 does not rename a key);
     the LeRobot configs still say ``ur5e_WristCamera_rgb_image`` (scripts/lerobot/configs/act_robot_button_push.yaml:24,47): see
-    ``mujoco_sim_amd.recording.REFERENCE_YAML_KEY_ALIASES``."""
+    ``mujoco_sim_amd.recording.REFERENCE_YAML_KEY_ALIASES``. ``depth_observations`` adds each camera's ``depth_map`` (float32 [H, W],
+    z-depth in metres, +inf where nothing is hit: the observable entities/camera.py:162 leaves as a TODO) right after its image."""
     if task == "point_mass_reach":
         state_keys = ("pointmass/position",)
     elif task == "robot_push_button":
@@ -113,7 +115,11 @@ def visual_observation_layout(task: str, action_type: str | None = None, image_r
     out = [(k, (n,), np.float64) for k, _, n in TASKS[task].obs_layout if k in state_keys]
     if use_wrist_camera and task == "robot_push_button":
         out.append(("ur5e/Camera/rgb_image", (r, r, 3), np.uint8))
+        if depth_observations:
+            out.append(("ur5e/Camera/depth_map", (r, r), np.float32))
     out.append(("Camera/rgb_image", (r, r, 3), np.uint8))
+    if depth_observations:
+        out.append(("Camera/depth_map", (r, r), np.float32))
     return out
 
 
@@ -126,7 +132,7 @@ class HipVectorEnv:
                  observation_type: str = STATE_OBS, image_resolution: int = 64, action_type: str | None = None,
                  button_disturbances: bool = False, use_wrist_camera: bool = True, n_objects: int | None = None,
                  max_episode_steps: int | None = None, block_shape: str = "mesh", global_num_envs: int | None = None,
-                 gripper_model: str = "reduced"):
+                 gripper_model: str = "reduced", cameraconfig=None, depth_observations: bool = False):
         if task not in TASKS:
             raise ValueError(f"unknown task {task!r}; available: {sorted(TASKS)}")
         self.spec = TASKS[task]
@@ -230,17 +236,26 @@ class HipVectorEnv:
         self.image_resolution = int(image_resolution)
         self._img = None
         self._wrist_img = None
+        self._depth = None
+        self._wrist_depth = None
+        self.depth_observations = bool(depth_observations)
+        if cameraconfig is not None:  # a CameraConfig (entities/camera.py): the scene camera's pose; its image size is image_resolution
+            self.set_scene_camera(cameraconfig.position, cameraconfig.orientation, cameraconfig.fov)
         self.use_wrist_camera = bool(use_wrist_camera) and task == "robot_push_button"
         if observation_type == VISUAL_OBS:
             r = self.image_resolution
             self._img = torch.zeros(N, r, r, 3, dtype=torch.uint8, device=dev)
             # point_reach.py:119-121 / robot_reach.py:139-141 / robot_push_button.py:113-124: proprioception +
             # camera image(s); dict order = composer's entity order (robot, wrist camera on the robot, scene camera)
-            layout = visual_observation_layout(task, action_type, r, self.use_wrist_camera)
-            self._visual_keys = tuple(k for k, shape, dt in layout if dt != np.uint8)
+            layout = visual_observation_layout(task, action_type, r, self.use_wrist_camera, self.depth_observations)
+            self._visual_keys = tuple(k for k, shape, dt in layout if dt == np.float64)
             if self.use_wrist_camera:
                 self._wrist_img = torch.zeros(N, r, r, 3, dtype=torch.uint8, device=dev)
-            spaces = [(k, Box(0, 255, shape=shape, dtype=np.uint8) if dt == np.uint8 else Box(-np.inf, np.inf, shape=shape, dtype=np.float64)) for k, shape, dt in layout]
+            if self.depth_observations:
+                self._depth = torch.zeros(N, r, r, dtype=torch.float32, device=dev)
+                if self.use_wrist_camera:
+                    self._wrist_depth = torch.zeros(N, r, r, dtype=torch.float32, device=dev)
+            spaces = [(k, Box(0, 255, shape=shape, dtype=np.uint8) if dt == np.uint8 else Box(0.0 if dt == np.float32 else -np.inf, np.inf, shape=shape, dtype=dt)) for k, shape, dt in layout]
             self.single_observation_space = Dict(OrderedDict(spaces))
             self.observation_space = Dict(OrderedDict((k, batch_box(s, N)) for k, s in self.single_observation_space.items()))
         if seed is not None:
@@ -260,11 +275,20 @@ class HipVectorEnv:
     def _obs_dict(self, flat):
         if self._img is not None and flat is self._buf["obs"]:
             # entity observables first (pointmass position, camera image), as in the reference's dict order
-            self.render(self.image_resolution, self.image_resolution, out=self._img)
+            r = self.image_resolution
+            if self._depth is None:
+                self.render(r, r, out=self._img)
+            else:  # one launch writes the image and its depth map
+                self.render_rgbd(r, r, out=(self._img, self._depth))
             d = OrderedDict((k, flat[..., s:s + n]) for k, s, n in self.spec.obs_layout if k in self._visual_keys)
             if self._wrist_img is not None:
-                d["ur5e/Camera/rgb_image"] = self.render(self.image_resolution, self.image_resolution, out=self._wrist_img, camera=1)
+                if self._wrist_depth is None:
+                    d["ur5e/Camera/rgb_image"] = self.render(r, r, out=self._wrist_img, camera=1)
+                else:
+                    d["ur5e/Camera/rgb_image"], d["ur5e/Camera/depth_map"] = self.render_rgbd(r, r, camera=1, out=(self._wrist_img, self._wrist_depth))
             d["Camera/rgb_image"] = self._img
+            if self._depth is not None:
+                d["Camera/depth_map"] = self._depth
             return d
         return OrderedDict((k, flat[..., s:s + n]) for k, s, n in self._state_layout)
 
@@ -340,6 +364,53 @@ class HipVectorEnv:
         assert out.shape == (self.num_envs, height, width, 3) and out.dtype == torch.uint8 and out.is_contiguous()
         nat.check(self._lib.mjs_render(self._h, int(camera), height, width, C.c_void_p(out.data_ptr()), self._stream()), self._h)
         return out
+
+    def render_depth(self, height: int = 64, width: int = 64, camera: int = 0, out: torch.Tensor | None = None) -> torch.Tensor:
+        """Depth maps of all envs, float32 [N, H, W] on the GPU (Camera.get_depth_map, entities/camera.py:105-114): z-depth in
+        metres, the nearest surface's distance along the optical axis as ``physics.render(depth=True)`` defines it, +inf where
+        the ray hits nothing. Same cameras as :meth:`render`."""
+        if out is None:
+            out = torch.empty(self.num_envs, height, width, dtype=torch.float32, device=self.device)
+        assert out.shape == (self.num_envs, height, width) and out.dtype == torch.float32 and out.is_contiguous()
+        nat.check(self._lib.mjs_render_rgbd(self._h, int(camera), height, width, None, C.c_void_p(out.data_ptr()), self._stream()), self._h)
+        return out
+
+    def render_rgbd(self, height: int = 64, width: int = 64, camera: int = 0, out: tuple | None = None):
+        """(rgb uint8 [N, H, W, 3], depth float32 [N, H, W]) from ONE launch: the image :meth:`render` gives and the depth map
+        :meth:`render_depth` gives. ``out`` = a pair of buffers to write into."""
+        rgb, depth = out if out is not None else (None, None)
+        if rgb is None:
+            rgb = torch.empty(self.num_envs, height, width, 3, dtype=torch.uint8, device=self.device)
+        if depth is None:
+            depth = torch.empty(self.num_envs, height, width, dtype=torch.float32, device=self.device)
+        assert rgb.shape == (self.num_envs, height, width, 3) and rgb.dtype == torch.uint8 and rgb.is_contiguous()
+        assert depth.shape == (self.num_envs, height, width) and depth.dtype == torch.float32 and depth.is_contiguous()
+        nat.check(self._lib.mjs_render_rgbd(self._h, int(camera), height, width, C.c_void_p(rgb.data_ptr()), C.c_void_p(depth.data_ptr()), self._stream()), self._h)
+        return rgb, depth
+
+    def set_scene_camera(self, position, orientation=None, fov=None):
+        """Pose of the task's scene camera (camera 0), the ``cameraconfig`` of the reference's task configs: world position,
+        MuJoCo quaternion (w, x, y, z; the camera looks along its local -z, +y is up; normalised by the library) and vertical
+        field of view in degrees. ``set_scene_camera(None)`` restores the task's default. The camera's own body moves with it;
+        the Button-Push wrist camera stays on the flange. The pose belongs to this handle: ``get_state`` / ``set_state`` do not
+        carry it."""
+        if position is None:
+            nat.check(self._lib.mjs_set_scene_camera(self._h, None), self._h)
+            return
+        if orientation is None or fov is None:
+            raise ValueError("set_scene_camera needs position, orientation and fov (or None alone for the task's default)")
+        pos = np.asarray(position, dtype=np.float64).reshape(-1)
+        quat = np.asarray(orientation, dtype=np.float64).reshape(-1)
+        if pos.shape != (3,) or quat.shape != (4,):
+            raise ValueError("position must have 3 numbers and orientation 4 (w, x, y, z)")
+        pose = nat.MjsCameraPose(pos=(C.c_double * 3)(*pos), quat=(C.c_double * 4)(*quat), fovy=float(fov))
+        nat.check(self._lib.mjs_set_scene_camera(self._h, C.byref(pose)), self._h)
+
+    def get_scene_camera(self):
+        """(position [3], orientation [4] normalised, fov) of the scene camera in use, as numpy float64 / float."""
+        pose = nat.MjsCameraPose()
+        nat.check(self._lib.mjs_get_scene_camera(self._h, C.byref(pose)), self._h)
+        return np.array(pose.pos, dtype=np.float64), np.array(pose.quat, dtype=np.float64), float(pose.fovy)
 
     def tcp_to_joints(self, tcp_positions, joint_guess):
         """Robot.get_joint_positions_from_tcp_pose for the top-down orientation (robot.py:140-151), batched on

@@ -1,6 +1,6 @@
 """Render-only timing (development tool): Button-Push at BASELINE config 5's shape (2048 envs, 64x64), the scene camera and
 the wrist camera timed separately with events on the launch stream after a few random steps (arms in varied poses).
-Run on the GPU box: python tools/render_bench.py [--envs 2048] [--res 64] [--reps 50]. MJS_LIB selects a diagnostic build."""
+Run on the GPU box: python tools/render_bench.py [--envs 2048] [--res 64] [--reps 50] [--depth]. MJS_LIB selects a diagnostic build."""
 import argparse
 import json
 import sys
@@ -18,6 +18,7 @@ def main():
     ap.add_argument("--res", type=int, default=64)
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--task", default="robot_push_button")
+    ap.add_argument("--depth", action="store_true", help="also time render_rgbd (image + depth map) and render_depth")
     a = ap.parse_args()
     venv = m.HipVectorEnv(a.task, a.envs, seed=11)
     venv.reset()
@@ -39,6 +40,19 @@ def main():
         torch.cuda.synchronize()
         ms = e0.elapsed_time(e1) / a.reps
         out[f"camera{cam}"] = {"ms": round(ms, 4), "GB/s": round(img.numel() / ms / 1e6, 1), "checksum": int(img.to(torch.int64).sum().item())}
+        if a.depth:  # the same render with the depth map (one launch), and the depth map alone
+            depth = torch.empty(a.envs, a.res, a.res, dtype=torch.float32, device="cuda")
+            for name, call in (("rgbd", lambda: venv.render_rgbd(a.res, a.res, camera=cam, out=(img, depth))),
+                               ("depth", lambda: venv.render_depth(a.res, a.res, camera=cam, out=depth))):
+                for _ in range(5):
+                    call()
+                torch.cuda.synchronize()
+                e0.record()
+                for _ in range(a.reps):
+                    call()
+                e1.record()
+                torch.cuda.synchronize()
+                out[f"camera{cam}"][f"{name}_ms"] = round(e0.elapsed_time(e1) / a.reps, 4)
     print(json.dumps(out))
 
 
