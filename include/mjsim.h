@@ -240,6 +240,43 @@ int mjs_debug_ur5e_ik(const double* T_dev, const double* guess_dev, double* q_de
  * Cartesian target into a Button-Push joint action (robot_push_button.py:287-291). */
 int mjs_ur5e_tcp_to_joints(const double* tcp_pos_dev, const double* guess_dev, double* q_dev, uint8_t* ok_dev, int32_t n, void* stream);
 
+/* The tasks' scripted demonstration policies on the device (entry points added after abi 3; mjs_config and the number stay as they
+ * are). Replaces the policy closures the reference's collector drives (scripts/demonstration_collection.py:303-345):
+ * PointMassReachTask.create_demonstation_policy (point_reach.py:227-240), create_demonstration_policy of robot_reach.py:222-253 and
+ * RobotPushButtonTask.create_demonstration_policy (robot_push_button.py:231-300). One launch for the handle's task and action type:
+ * obs_dev float64 [N, obs_dim] (layout: mjs_obs_dim; what the last reset / step wrote) -> actions_dev float64 [N, action_dim],
+ * ik_ok_dev uint8 [N] or NULL. Button-Push with MJS_ACTION_ABS_JOINT runs the IK of mjs_ur5e_tcp_to_joints inside the same launch
+ * (guess = the joints in obs); where no solution exists the action holds the current joints and ik_ok is 0 (the reference
+ * raises); ik_ok is 1 wherever no IK was needed. Noise: the reference draws it from the global np.random (no env stream, so
+ * nothing to reproduce); the caller passes standard-normal draws noise_z_dev, float64 [N, 2] for Pointmass (a *= 1 + noise * z) or
+ * [N, 3] for Robot-Reach (d += noise * z); NULL or noise == 0: none; Button-Push ignores both. MJS_ERR_INVALID_ARG for a negative or
+ * non-finite noise; MJS_ERR_UNSUPPORTED for Planar-Push, whose "demonstration policy" is a keyboard teleop
+ * (robot_planar_push.py:288-308). */
+int mjs_demonstration_actions(mjs_handle* h, const double* obs_dev, const double* noise_z_dev, double noise, double* actions_dev, uint8_t* ik_ok_dev,
+                              void* stream);
+
+/* What a closed-loop demonstration rollout writes besides mjs_outputs, and its noise. */
+typedef struct {
+  uint32_t struct_size;        /* sizeof(mjs_demo_rollout), validated like mjs_config's */
+  int32_t height, width;       /* of the image buffers; ignored when both are NULL */
+  int32_t reserved0;           /* 0 */
+  double noise;                /* as in mjs_demonstration_actions */
+  const double* noise_z_dev;   /* [T, N, k] (k = 2 Pointmass, 3 Robot-Reach) or NULL */
+  double* actions_out_dev;     /* [T, N, action_dim], required: the action the policy chose at every step */
+  uint8_t* ik_ok_dev;          /* [T, N] or NULL */
+  uint8_t* scene_rgb_dev;      /* [T, N, height, width, 3] or NULL: MJS_CAMERA_SCENE before every step */
+  uint8_t* wrist_rgb_dev;      /* the same for MJS_CAMERA_WRIST (Button-Push only) */
+} mjs_demo_rollout;            /* 64 bytes */
+/* The collector's loop (demonstration_collection.py:303-345) for T control steps without returning to the host: before step t the
+ * policy reads the observation of step t-1 (slice t-1 of out->obs; obs0_dev, the observation the caller's last reset or step
+ * wrote, for t = 0) and writes slice t of demo->actions_out_dev (and of ik_ok_dev); the cameras, where buffers are given, are
+ * rendered next (slice t = the frame BEFORE the action, which is what the recorder stores; the launches of mjs_render); then the
+ * ordinary step launch writes slice t of out, sliced as mjs_rollout slices it. 2 launches per step without images. out->obs and
+ * demo->actions_out_dev are required (MJS_ERR_INVALID_ARG otherwise, as for T < 0, a wrong struct_size, a wrist buffer on a task
+ * without a wrist camera, image buffers without a positive size, or obs0_dev NULL with T > 0); T == 0 does nothing and returns 0.
+ * MJS_ERR_UNSUPPORTED for Planar-Push. */
+int mjs_rollout_demonstration(mjs_handle* h, const double* obs0_dev, int32_t T, const mjs_demo_rollout* demo, const mjs_outputs* out, void* stream);
+
 /* Replaces the Robot entity's control API on a stand-alone UR5e (entities/robots/robot.py:198-272): Robot.moveJ :211-216,
  * Robot.movej_IK :198-209, Robot.servoL :218-225, Robot.servoJ :227-259, then n_substeps x (Robot.before_substep :261-272 +
  * JointTrajectory.get_target_joint_positions joint_trajectory.py:41-47; Physics.step), then Robot.get_tcp_pose :153-168.

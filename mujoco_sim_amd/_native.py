@@ -40,6 +40,7 @@ EXPORTED_SYMBOLS = [
     "mjs_version", "mjs_obs_dim", "mjs_action_dim", "mjs_action_dim_for", "mjs_state_dim", "mjs_env_obs_dim", "mjs_env_state_dim", "mjs_algorithmic_bytes_per_env_step", "mjs_env_algorithmic_bytes_per_env_step", "mjs_substeps",
     "mjs_create", "mjs_destroy", "mjs_last_error", "mjs_seed", "mjs_reset", "mjs_step", "mjs_rollout",
     "mjs_get_state", "mjs_set_state", "mjs_get_rng_state", "mjs_set_rng_state", "mjs_render", "mjs_set_scene_camera", "mjs_get_scene_camera", "mjs_render_rgbd", "mjs_debug_ur5e_ik", "mjs_ur5e_tcp_to_joints", "mjs_ur5e_robot_run",
+    "mjs_demonstration_actions", "mjs_rollout_demonstration",
 ]
 
 
@@ -73,6 +74,18 @@ class MjsCameraPose(C.Structure):
         super().__init__(*args, **kw)
         if "struct_size" not in kw:
             self.struct_size = C.sizeof(MjsCameraPose)
+
+
+class MjsDemoRollout(C.Structure):
+    """mjs_demo_rollout: what a closed-loop demonstration rollout writes besides MjsOutputs (actions, ik_ok, camera frames), and its noise."""
+    _fields_ = [("struct_size", C.c_uint32), ("height", C.c_int32), ("width", C.c_int32), ("reserved0", C.c_int32), ("noise", C.c_double),
+                ("noise_z_dev", C.c_void_p), ("actions_out_dev", C.c_void_p), ("ik_ok_dev", C.c_void_p), ("scene_rgb_dev", C.c_void_p),
+                ("wrist_rgb_dev", C.c_void_p)]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        if "struct_size" not in kw:
+            self.struct_size = C.sizeof(MjsDemoRollout)
 
 
 class MjsError(RuntimeError):
@@ -181,6 +194,8 @@ def lib() -> C.CDLL:
     L.mjs_set_scene_camera.argtypes = [C.c_void_p, C.POINTER(MjsCameraPose)]
     L.mjs_get_scene_camera.argtypes = [C.c_void_p, C.POINTER(MjsCameraPose)]
     L.mjs_render_rgbd.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.mjs_demonstration_actions.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.mjs_rollout_demonstration.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(MjsDemoRollout), C.POINTER(MjsOutputs), C.c_void_p]
     L.mjs_get_rng_state.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.mjs_set_rng_state.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = L

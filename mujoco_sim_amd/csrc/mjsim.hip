@@ -15,6 +15,7 @@
 #include "mjs_gripper14.h"
 #include "mjs_push.h"
 #include "mjs_render.h"
+#include "mjs_policy.h"
 #ifdef MJS_STAMPS
 #include "mjs_stamps_report.h"
 #endif
@@ -408,6 +409,53 @@ int render_launch(mjs_handle* h, rend::RenderParams& p, float* depth, bool wrist
   return MJS_OK;
 }
 
+// slice t of rollout outputs (every field carries a leading time axis [T, N, ...])
+mjs_outputs slice_outputs(const mjs_handle* h, const mjs_outputs* out, int32_t t) {
+  mjs_outputs o;
+  std::memset(&o, 0, sizeof o);
+  if (!out) return o;
+  const size_t N = (size_t)h->cfg.num_envs;
+  o = *out;
+  if (o.obs) o.obs += (size_t)t * N * h->inst.obs_dim;
+  if (o.terminal_obs) o.terminal_obs += (size_t)t * N * h->inst.obs_dim;
+  if (o.reward) o.reward += t * N;
+  if (o.discount) o.discount += t * N;
+  if (o.terminated) o.terminated += t * N;
+  if (o.truncated) o.truncated += t * N;
+  if (o.is_success) o.is_success += t * N;
+  if (o.step_type) o.step_type += t * N;
+  if (o.fault) o.fault += t * N;
+  if (o.ncon) o.ncon += t * N;
+  return o;
+}
+
+// one launch of the demonstration-policy kernel (mjs_policy.h) for the handle's task and action type; arguments validated by the callers
+int launch_policy(mjs_handle* h, const double* obs, const double* z, double noise, double* actions, uint8_t* ik_ok, hipStream_t s) {
+  pol::PolicyParams p;
+  p.N = h->cfg.num_envs;
+  p.task = h->cfg.task;
+  p.action_type = h->cfg.action_type;
+  p.obs_dim = h->inst.obs_dim;
+  p.act_dim = h->inst.act_dim;
+  p.noise = noise;
+  p.obs = obs;
+  p.z = noise != 0 ? z : nullptr;
+  p.actions = actions;
+  p.ik_ok = ik_ok;
+  pol::kernel<<<grid_for(p.N), BLOCK, 0, s>>>(p);
+  HIP_TRY(h, hipGetLastError());
+  return MJS_OK;
+}
+// what both policy entry points refuse; nullptr = fine
+const char* policy_refusal(const mjs_handle* h, double noise, int& code) {
+  code = MJS_ERR_UNSUPPORTED;
+  if (h->cfg.task == MJS_TASK_PLANAR_PUSH)
+    return "Planar-Push has no scripted demonstration policy (the reference's is a keyboard teleop, robot_planar_push.py:288-308)";
+  code = MJS_ERR_INVALID_ARG;
+  if (!(noise >= 0) || !std::isfinite(noise)) return "noise must be finite and >= 0";
+  return nullptr;
+}
+
 }  // namespace
 
 extern "C" {
@@ -561,22 +609,58 @@ int mjs_rollout(mjs_handle* h, const double* actions_dev, int32_t T, const mjs_o
   h->prims_valid = false;
   const size_t N = (size_t)h->cfg.num_envs;
   for (int32_t t = 0; t < T; t++) {
-    mjs_outputs o;
-    std::memset(&o, 0, sizeof o);
-    if (out) {
-      o = *out;
-      if (o.obs) o.obs += (size_t)t * N * h->inst.obs_dim;
-      if (o.terminal_obs) o.terminal_obs += (size_t)t * N * h->inst.obs_dim;
-      if (o.reward) o.reward += t * N;
-      if (o.discount) o.discount += t * N;
-      if (o.terminated) o.terminated += t * N;
-      if (o.truncated) o.truncated += t * N;
-      if (o.is_success) o.is_success += t * N;
-      if (o.step_type) o.step_type += t * N;
-      if (o.fault) o.fault += t * N;
-      if (o.ncon) o.ncon += t * N;
-    }
+    const mjs_outputs o = slice_outputs(h, out, t);
     int rc = launch<false>(h, make_params(h, actions_dev + (size_t)t * N * h->inst.act_dim, nullptr, &o), (hipStream_t)stream);
+    if (rc != MJS_OK) return rc;
+  }
+  return MJS_OK;
+}
+
+// ---- demonstration policies ----------------------------------------------------------------------------------------------
+int mjs_demonstration_actions(mjs_handle* h, const double* obs_dev, const double* noise_z_dev, double noise, double* actions_dev, uint8_t* ik_ok_dev,
+                              void* stream) {
+  if (!h) return fail(nullptr, MJS_ERR_INVALID_ARG, "mjs_demonstration_actions: null handle");
+  int code;
+  if (const char* why = policy_refusal(h, noise, code)) return fail(h, code, std::string("mjs_demonstration_actions: ") + why);
+  if (!obs_dev || !actions_dev) return fail(h, MJS_ERR_INVALID_ARG, "mjs_demonstration_actions: obs_dev or actions_dev is null");
+  DeviceGuard dev_(h->cfg.device);
+  HIP_TRY(h, dev_.err);
+  return launch_policy(h, obs_dev, noise_z_dev, noise, actions_dev, ik_ok_dev, (hipStream_t)stream);
+}
+
+int mjs_rollout_demonstration(mjs_handle* h, const double* obs0_dev, int32_t T, const mjs_demo_rollout* demo, const mjs_outputs* out, void* stream) {
+  if (!h) return fail(nullptr, MJS_ERR_INVALID_ARG, "mjs_rollout_demonstration: null handle");
+  if (!demo) return fail(h, MJS_ERR_INVALID_ARG, "mjs_rollout_demonstration: demo is null");
+  if (demo->struct_size != sizeof(mjs_demo_rollout))
+    return fail(h, MJS_ERR_INVALID_ARG, "mjs_rollout_demonstration: mjs_demo_rollout.struct_size does not match this library's header");
+  int code;
+  if (const char* why = policy_refusal(h, demo->noise, code)) return fail(h, code, std::string("mjs_rollout_demonstration: ") + why);
+  if (T < 0) return fail(h, MJS_ERR_INVALID_ARG, "mjs_rollout_demonstration: T is negative");
+  if (!out || !out->obs) return fail(h, MJS_ERR_INVALID_ARG, "mjs_rollout_demonstration: out->obs is required (the policy of step t reads slice t-1)");
+  if (!demo->actions_out_dev) return fail(h, MJS_ERR_INVALID_ARG, "mjs_rollout_demonstration: demo->actions_out_dev is required");
+  if (demo->wrist_rgb_dev && h->cfg.task != MJS_TASK_BUTTON_PUSH)
+    return fail(h, MJS_ERR_INVALID_ARG, "mjs_rollout_demonstration: a wrist image buffer on a task without a wrist camera");
+  const bool images = demo->scene_rgb_dev || demo->wrist_rgb_dev;
+  if (images && (demo->height <= 0 || demo->width <= 0)) return fail(h, MJS_ERR_INVALID_ARG, "mjs_rollout_demonstration: image buffers need a positive height and width");
+  if (T == 0) return MJS_OK;
+  if (!obs0_dev) return fail(h, MJS_ERR_INVALID_ARG, "mjs_rollout_demonstration: obs0_dev is null");
+  DeviceGuard dev_(h->cfg.device);
+  HIP_TRY(h, dev_.err);
+  const size_t N = (size_t)h->cfg.num_envs, A = (size_t)h->inst.act_dim, O = (size_t)h->inst.obs_dim;
+  const size_t k = h->cfg.task == MJS_TASK_POINTMASS_REACH ? 2 : 3;  // noise draws per env
+  const size_t frame = images ? N * (size_t)demo->height * (size_t)demo->width * 3 : 0;
+  for (int32_t t = 0; t < T; t++) {
+    const double* obs = t == 0 ? obs0_dev : out->obs + (size_t)(t - 1) * N * O;
+    double* actions = demo->actions_out_dev + (size_t)t * N * A;
+    int rc = launch_policy(h, obs, demo->noise_z_dev ? demo->noise_z_dev + (size_t)t * N * k : nullptr, demo->noise, actions,
+                           demo->ik_ok_dev ? demo->ik_ok_dev + (size_t)t * N : nullptr, (hipStream_t)stream);
+    if (rc != MJS_OK) return rc;
+    // the frames of the state the policy has just looked at
+    if (demo->scene_rgb_dev && (rc = mjs_render(h, MJS_CAMERA_SCENE, demo->height, demo->width, demo->scene_rgb_dev + (size_t)t * frame, stream)) != MJS_OK) return rc;
+    if (demo->wrist_rgb_dev && (rc = mjs_render(h, MJS_CAMERA_WRIST, demo->height, demo->width, demo->wrist_rgb_dev + (size_t)t * frame, stream)) != MJS_OK) return rc;
+    const mjs_outputs o = slice_outputs(h, out, t);
+    h->prims_valid = false;
+    rc = launch<false>(h, make_params(h, actions, nullptr, &o), (hipStream_t)stream);
     if (rc != MJS_OK) return rc;
   }
   return MJS_OK;

@@ -1,8 +1,8 @@
 """Robot-Reach task description (host side).
 
 Mirrors ``mujoco_sim/environments/tasks/robot_reach.py:33-83`` (RobotReachConfig dataclass:
-same fields and defaults) and the task constructor at :85-132. Physics and task logic run in
-csrc/mjs_reach.h.
+same fields and defaults), the task constructor at :85-132 and the module-level demonstration policy at
+:222-253. Physics and task logic run in csrc/mjs_reach.h, the policy in csrc/mjs_policy.h.
 """
 from __future__ import annotations
 
@@ -84,3 +84,22 @@ class RobotReachTask:
             return np.random.uniform(spec.minimum, spec.maximum, spec.shape)
 
         return random_policy
+
+    def demonstration_actions(self, venv, noise_level: float = 0.0, generator=None):
+        """One batched step of the reference's demonstration policy (robot_reach.py:240-249) for every env of ``venv`` (a
+        HipVectorEnv of this task), computed on the device (csrc/mjs_policy.h): the TCP position plus the difference to the target,
+        with ``noise_level`` times a standard-normal draw added to the difference and the reference's speed clamp."""
+        return venv.demonstration_actions(noise=noise_level, generator=generator)[0]
+
+
+def create_demonstration_policy(environment, noise_level=0.0):
+    """robot_reach.py:222-253, module-level as there: policy(time_step) -> absolute TCP target (numpy) for a single-env
+    ``HipEnvironment`` of this task (or a ``HipVectorEnv``, whose env 0 it then drives)."""
+    venv = environment._venv if hasattr(environment, "_venv") else environment
+    task = getattr(environment, "task", None)
+    assert task is None or isinstance(task, RobotReachTask)  # robot_reach.py:225
+
+    def demonstration_policy(time_step=None):
+        return venv.demonstration_actions(noise=noise_level)[0][0].cpu().numpy()
+
+    return demonstration_policy

@@ -8,7 +8,8 @@ observations). The reference delegates storage to the third-party ``lerobot`` pa
 writes the LeRobot v2 directory layout itself with pyarrow: ``data/chunk-000/episode_XXXXXX.parquet``,
 ``meta/info.json``, ``meta/episodes.jsonl``, ``meta/tasks.jsonl`` (images as raw uint8 columns, i.e. the reference's
 ``use_videos=False`` mode; no video encoder is available). ``record_batch`` is the batched path: it takes the
-outputs of one ``HipVectorEnv.step`` for all N envs and closes an episode whenever an env reports LAST.
+outputs of one ``HipVectorEnv.step`` for all N envs and closes an episode whenever an env reports LAST; ``record_rollout``
+consumes a whole ``HipVectorEnv.demonstration_rollout`` block with array slicing per episode.
 """
 from __future__ import annotations
 
@@ -73,6 +74,9 @@ class LeRobotDatasetRecorder:
         (self.root_dataset_dir / "data" / "chunk-000").mkdir(parents=True, exist_ok=True)
         self._frames = []          # single-env path
         self._batch_frames = None  # batched path: per-env lists
+        # record_rollout: where the state keys sit in a flat observation row, and whether the handle resets its envs by itself
+        self._flat_layout = getattr(env, "flat_observation_layout", None)
+        self._autoreset = getattr(env, "autoreset", "next_step")
 
     # ------------------------------------------------------------------ single-env API of the reference
     def start_episode(self):
@@ -119,28 +123,76 @@ class LeRobotDatasetRecorder:
                 self._write_episode(self._batch_frames[i])
                 self._batch_frames[i] = []
 
+    # ------------------------------------------------------------------ whole rollout blocks (HipVectorEnv.demonstration_rollout)
+    def record_rollout(self, block, obs0, seeds=None):
+        """One ``HipVectorEnv.demonstration_rollout`` block: ``block`` = its dict of [T, N, ...] arrays (``obs`` flat rows,
+        ``actions``, ``reward``, ``is_success``, ``step_type``, and the camera frames under their observation keys when the
+        recorder's env has image keys), ``obs0`` [N, obs_dim] = ``flat_obs`` as it was BEFORE the rollout. For env i the frames
+        are the rows t with ``step_type[t, i] != FIRST`` (a FIRST row is a reset and applied no action); the stored observation
+        of row t is row t-1's (``obs0`` for t = 0), the stored images are the block's frames of row t (taken before the
+        action); an episode closes on LAST. **An episode still open at the end of the block is dropped** (a block that
+        begins in mid-episode records the rest of that episode as an episode of its own): start blocks at a reset and make them
+        long enough. On a handle with
+        ``autoreset="disabled"`` only each env's first episode of the block is recorded (the env goes on stepping a finished
+        episode). Writes the files a ``record_batch`` loop over the same data writes, without a Python object per frame."""
+        if self._flat_layout is None:
+            raise ValueError("record_rollout needs an env with flat_observation_layout (a HipVectorEnv)")
+        from . import _native as nat
+
+        step_type = _to_numpy(block["step_type"])
+        T, n = step_type.shape
+        obs = _to_numpy(block["obs"])
+        prev = np.concatenate([_to_numpy(obs0)[None], obs[:-1]], axis=0) if T else obs  # the observation BEFORE each row's action
+        actions, reward, success = (_to_numpy(block[k]) for k in ("actions", "reward", "is_success"))
+        images = {k: _to_numpy(block[k]) for k in self.image_keys}
+        closes = []  # (row of the LAST, env, rows of the episode)
+        for i in range(n):
+            rows = np.flatnonzero(step_type[:, i] != nat.STEP_FIRST)
+            ends = np.flatnonzero(step_type[rows, i] == nat.STEP_LAST)
+            if self._autoreset == "disabled":
+                ends = ends[:1]
+            start = 0
+            for e in ends:
+                closes.append((int(rows[e]), i, rows[start:e + 1]))
+                start = e + 1
+        for _, i, rows in sorted(closes, key=lambda c: c[:2]):  # the order in which a step-by-step recorder closes them
+            L = len(rows)
+            cols = {"action": actions[rows, i].astype(np.float32).reshape(L, -1), "next.reward": reward[rows, i].astype(np.float32).reshape(L, 1),
+                    "next.success": success[rows, i].astype(bool).reshape(L, 1), "seed": np.full((L, 1), 0 if seeds is None else int(seeds[i]), np.int64),
+                    "timestamp": (np.arange(L) / self.fps).astype(np.float32).reshape(L, 1)}
+            for key in self.image_keys:
+                cols[self.key_mapping_dict[key]] = images[key][rows, i].astype(np.uint8)
+            where = {key: slice(s, s + width) for key, s, width in self._flat_layout}
+            state = [prev[rows, i, where[key]].astype(np.float32) for key in self.state_keys]
+            for key, v in zip(self.state_keys, state):
+                cols[self.key_mapping_dict[key]] = v
+            cols["observation.state"] = np.concatenate(state, axis=1) if state else np.zeros((L, 0), np.float32)
+            self._write_columns(cols, L)
+
     # ------------------------------------------------------------------ storage
     def _write_episode(self, frames):
+        if frames:
+            self._write_columns({key: np.stack([f[key] for f in frames]) for key in self.features}, len(frames))
+
+    def _write_columns(self, columns, n):
+        """One episode from its columns: {feature: [n, ...] array}."""
         import pyarrow as pa
         import pyarrow.parquet as pq
 
-        if not frames:
-            return
         ep = self._n_recorded_episodes
         cols = {}
-        for key, feat in self.features.items():
-            stacked = np.stack([f[key] for f in frames])
-            flat = stacked.reshape(len(frames), -1)
+        for key in self.features:
+            flat = columns[key].reshape(n, -1)
             cols[key] = pa.FixedSizeListArray.from_arrays(pa.array(flat.ravel()), flat.shape[1])
-        cols["episode_index"] = pa.array(np.full(len(frames), ep, np.int64))
-        cols["frame_index"] = pa.array(np.arange(len(frames), dtype=np.int64))
-        cols["index"] = pa.array(np.arange(self._n_frames, self._n_frames + len(frames), dtype=np.int64))
-        cols["task_index"] = pa.array(np.zeros(len(frames), np.int64))
+        cols["episode_index"] = pa.array(np.full(n, ep, np.int64))
+        cols["frame_index"] = pa.array(np.arange(n, dtype=np.int64))
+        cols["index"] = pa.array(np.arange(self._n_frames, self._n_frames + n, dtype=np.int64))
+        cols["task_index"] = pa.array(np.zeros(n, np.int64))
         pq.write_table(pa.table(cols), self.root_dataset_dir / "data" / "chunk-000" / f"episode_{ep:06d}.parquet")
         with open(self.root_dataset_dir / "meta" / "episodes.jsonl", "a") as f:
-            f.write(json.dumps({"episode_index": ep, "tasks": [self.task], "length": len(frames)}) + "\n")
+            f.write(json.dumps({"episode_index": ep, "tasks": [self.task], "length": n}) + "\n")
         self._n_recorded_episodes += 1
-        self._n_frames += len(frames)
+        self._n_frames += n
 
     def finish_recording(self):
         info = {"codebase_version": "v2.0", "repo_id": self.dataset_name, "fps": self.fps, "total_episodes": self._n_recorded_episodes,

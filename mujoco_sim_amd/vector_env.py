@@ -345,6 +345,74 @@ class HipVectorEnv:
         nat.check(self._lib.mjs_rollout(self._h, C.c_void_p(a.data_ptr()), T, C.byref(out), self._stream()), self._h)
         return {k: v for k, v in buf.items() if v is not None}
 
+    # ------------------------------------------------------------------ scripted demonstration policies on the device
+    _NOISE_DRAWS = {"point_mass_reach": 2, "robot_reach": 3}  # standard-normal draws per env and step (csrc/mjs_policy.h)
+
+    def _noise_z(self, noise, generator, lead=()):
+        k = self._NOISE_DRAWS.get(self.spec.name, 0)
+        if not noise or not k:
+            return None
+        return torch.randn(*lead, self.num_envs, k, dtype=torch.float64, device=self.device, generator=generator)
+
+    def demonstration_actions(self, noise: float = 0.0, generator: torch.Generator | None = None, out: torch.Tensor | None = None):
+        """The task's scripted demonstration policy (point_reach.py:227-240, robot_reach.py:222-253, robot_push_button.py:231-300)
+        for every env, from ``flat_obs``, in ONE launch: ``(actions [N, A] float64, ik_ok [N] bool)``. Button-Push joint actions
+        run the IK inside that launch; where it finds no solution the action holds the current joints and ``ik_ok`` is False.
+        ``noise``: the reference's ``noise`` / ``noise_level`` (Pointmass, Robot-Reach; Button-Push has none); its standard-normal
+        draws come from ``torch.randn(..., generator=generator)`` on the device. ``out``: the action buffer to write."""
+        if out is None:
+            out = torch.empty(self.num_envs, self.action_dim, dtype=torch.float64, device=self.device)
+        assert out.shape == (self.num_envs, self.action_dim) and out.dtype == torch.float64 and out.is_contiguous()
+        ok = torch.empty(self.num_envs, dtype=torch.uint8, device=self.device)
+        z = self._noise_z(noise, generator)
+        nat.check(self._lib.mjs_demonstration_actions(self._h, self._buf["obs"].data_ptr(), z.data_ptr() if z is not None else None, float(noise),
+                                                      out.data_ptr(), ok.data_ptr(), self._stream()), self._h)
+        return out, ok.bool()
+
+    def demonstration_rollout(self, T: int, noise: float = 0.0, generator: torch.Generator | None = None, render: bool = False,
+                              keep: tuple = ("obs", "reward", "terminated", "truncated", "is_success", "step_type", "fault", "ncon", "discount")):
+        """T closed-loop control steps of the scripted policy without returning to Python: per step one policy launch (it reads the
+        previous step's observation; ``flat_obs`` for the first) and the ordinary step launch. Returns :meth:`rollout`'s dict of
+        [T, N, ...] tensors plus ``"actions"`` [T, N, A] and ``"ik_ok"`` [T, N] bool; ``render=True`` adds the camera frames taken
+        BEFORE every step (uint8 [T, N, R, R, 3], R = ``image_resolution``) under the keys of :func:`visual_observation_layout`.
+        Equal, bit for bit, to T x (``demonstration_actions``; ``step``). Afterwards ``flat_obs`` holds the block's last
+        observation, so that calls chain; a caller that records the block (``LeRobotDatasetRecorder.record_rollout``) clones
+        ``flat_obs`` first: it is the observation of the block's first frame."""
+        T = int(T)
+        if T < 0:
+            raise ValueError("T must not be negative")
+        N, dev = self.num_envs, self.device
+        keep = tuple(keep) + ("obs",)  # step t's policy reads slice t-1
+        buf = {k: (torch.zeros((T,) + tuple(v.shape), dtype=v.dtype, device=dev) if k in keep else None) for k, v in self._buf.items()}
+        actions = torch.zeros(T, N, self.action_dim, dtype=torch.float64, device=dev)
+        ok = torch.ones(T, N, dtype=torch.uint8, device=dev)
+        z = self._noise_z(noise, generator, lead=(T,))
+        images = {}
+        if render:
+            r = self.image_resolution
+            if self.use_wrist_camera:
+                images["ur5e/Camera/rgb_image"] = torch.zeros(T, N, r, r, 3, dtype=torch.uint8, device=dev)
+            images["Camera/rgb_image"] = torch.zeros(T, N, r, r, 3, dtype=torch.uint8, device=dev)
+        if T:  # (an empty block needs no launch, and empty tensors have no address to pass)
+            ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+            demo = nat.MjsDemoRollout(height=self.image_resolution, width=self.image_resolution, noise=float(noise), noise_z_dev=ptr(z),
+                                      actions_out_dev=actions.data_ptr(), ik_ok_dev=ok.data_ptr(),
+                                      scene_rgb_dev=ptr(images.get("Camera/rgb_image")), wrist_rgb_dev=ptr(images.get("ur5e/Camera/rgb_image")))
+            out = self._make_outputs(buf)
+            nat.check(self._lib.mjs_rollout_demonstration(self._h, self._buf["obs"].data_ptr(), T, C.byref(demo), C.byref(out), self._stream()), self._h)
+            self._buf["obs"].copy_(buf["obs"][-1])
+        res = {k: v for k, v in buf.items() if v is not None}
+        res["actions"], res["ik_ok"] = actions, ok.bool()
+        res.update(images)
+        return res
+
+    @property
+    def flat_observation_layout(self) -> tuple:
+        """((key, start, length), ...) of the state keys of this handle's observation dict inside a ``flat_obs`` row."""
+        if self._img is not None:
+            return tuple(e for e in self.spec.obs_layout if e[0] in self._visual_keys)
+        return tuple(self._state_layout)
+
     def get_state(self) -> torch.Tensor:
         s = torch.empty(self.state_dim, self.num_envs, dtype=torch.float64, device=self.device)
         nat.check(self._lib.mjs_get_state(self._h, C.c_void_p(s.data_ptr()), self._stream()), self._h)
