@@ -277,6 +277,74 @@ typedef struct {
  * MJS_ERR_UNSUPPORTED for Planar-Push. */
 int mjs_rollout_demonstration(mjs_handle* h, const double* obs0_dev, int32_t T, const mjs_demo_rollout* demo, const mjs_outputs* out, void* stream);
 
+/* A learned policy on the device (entry points added after abi 3; mjs_config and the number stay as they are): the MLP actor of SAC
+ * as the reference's RL scripts configure it (scripts/sb3/reach_sac.py, planar_push.py, sb3_sac.py: net_arch pi = [64, 64] / [32],
+ * SB3's default [256, 256]; stable_baselines3/sac/policies.py Actor), evaluated for every env of a handle in ONE launch
+ * (csrc/mjs_actor.h), in float32 with float32 accumulation, as SB3 evaluates it:
+ *   x_j = (float) obs[i, obs_index[j]]   j < in_dim            h_l = act(W_l h_{l-1} + b_l)   l = 1..n_hidden
+ *   mu = W_mu h + b_mu    ls = clamp(W_ls h + b_ls, -20, 2)     u = mu (z NULL) or mu + expf(ls) * z[i]
+ *   a = tanhf(u) -> squashed_out (what a replay buffer stores)  actions = low + 0.5 * ((double) a + 1.0) * (high - low)  in float64
+ * An actor belongs to a device, not to a handle: any handle of that device whose action width is action_dim and whose observation
+ * row holds every obs_index entry may use it. */
+typedef struct mjs_actor mjs_actor;
+enum { MJS_ACTIVATION_RELU = 0, MJS_ACTIVATION_TANH = 1 };
+enum { MJS_ACTOR_VARIANT_DEFAULT = 0 /* 16 envs per workgroup on v_mfma_f32_16x16x4_f32 */,
+       MJS_ACTOR_VARIANT_TILE32 = 1 /* 32 envs per workgroup on v_mfma_f32_32x32x2_f32: results equal to rounding (another summation
+                                       order over k); for A/B measurements */ };
+typedef struct {
+  uint32_t struct_size;      /* sizeof(mjs_actor_desc), validated like mjs_config's */
+  int32_t device;            /* HIP device ordinal */
+  int32_t in_dim;            /* 1..64 */
+  int32_t n_hidden;          /* 1..3 */
+  int32_t hidden[3];         /* widths, each 1..256; entries past n_hidden are ignored */
+  int32_t action_dim;        /* 1..8; must equal the action width of every handle the actor is used with */
+  int32_t activation;        /* MJS_ACTIVATION_* */
+  int32_t variant;           /* MJS_ACTOR_VARIANT_* */
+  const int32_t* obs_index;  /* HOST int32 [in_dim], copied: the column of a flat observation row that feeds input j; each >= 0 */
+} mjs_actor_desc;            /* 48 bytes */
+/* Allocates the packed weight buffers and nothing else. MJS_ERR_INVALID_ARG (text in mjs_last_error(NULL)) for a wrong struct_size,
+ * a null pointer, or in_dim, n_hidden, a width, action_dim, activation, variant or an obs_index entry out of range. */
+int mjs_actor_create(const mjs_actor_desc* desc, mjs_actor** out);
+void mjs_actor_destroy(mjs_actor* actor);
+/* DEVICE pointers to float32 parameters in torch.nn.Linear layout: weight [out, in] row-major, bias [out]. */
+typedef struct {
+  uint32_t struct_size;        /* sizeof(mjs_actor_weights) */
+  int32_t reserved0;           /* 0 */
+  const float* hidden_w[3];    /* layer l: [hidden[l], l == 0 ? in_dim : hidden[l-1]]; entries past n_hidden are ignored */
+  const float* hidden_b[3];
+  const float *mu_w, *mu_b;    /* [action_dim, hidden[n_hidden-1]], [action_dim] */
+  const float *log_std_w, *log_std_b;
+} mjs_actor_weights;           /* 88 bytes */
+/* Packs the parameters into the actor's own K-major copy with small kernels on the caller's stream; never synchronises (a training
+ * loop calls it after every policy update; launches that use the actor are ordered after it by the stream). */
+int mjs_actor_load(mjs_actor* actor, const mjs_actor_weights* weights, void* stream);
+/* One launch: obs_dev float64 [N, obs_dim] (what the last reset / step wrote) -> actions_dev float64 [N, action_dim] and, unless
+ * NULL, squashed_out_dev float32 [N, action_dim]. z_dev: float32 [N, action_dim] standard-normal draws, or NULL for the
+ * deterministic action. low / high: HOST float64 [action_dim], the action space's bounds. MJS_ERR_INVALID_ARG (nothing launched)
+ * for a null required pointer, an obs_index entry outside the handle's mjs_env_obs_dim, an action_dim other than the handle's, an
+ * actor of another device, or an actor that was never loaded. All four tasks. */
+int mjs_actor_actions(mjs_handle* h, const mjs_actor* actor, const double* obs_dev, const float* z_dev, const double* low, const double* high,
+                      double* actions_dev, float* squashed_out_dev, void* stream);
+typedef struct {
+  uint32_t struct_size;        /* sizeof(mjs_actor_rollout) */
+  int32_t height, width;       /* of the image buffers; ignored when both are NULL */
+  int32_t reserved0;           /* 0 */
+  const float* z_dev;          /* [T, N, action_dim] or NULL (deterministic) */
+  const double* low;           /* HOST [action_dim] */
+  const double* high;          /* HOST [action_dim] */
+  double* actions_out_dev;     /* [T, N, action_dim], required */
+  float* squashed_out_dev;     /* [T, N, action_dim] or NULL */
+  uint8_t* scene_rgb_dev;      /* [T, N, height, width, 3] or NULL: MJS_CAMERA_SCENE before every step */
+  uint8_t* wrist_rgb_dev;      /* the same for MJS_CAMERA_WRIST (Button-Push only) */
+} mjs_actor_rollout;           /* 72 bytes */
+/* mjs_rollout_demonstration with the actor as the policy, clause for clause (the same loop): before step t the actor reads the
+ * observation of step t-1 (slice t-1 of out->obs; obs0_dev for t = 0) and writes slice t of actions_out_dev (and of
+ * squashed_out_dev); the cameras, where buffers are given, are rendered next; then the ordinary step launch writes slice t of
+ * out. 2 launches per step without images. The refusals of mjs_rollout_demonstration and of mjs_actor_actions; T == 0 does nothing
+ * and returns 0. All four tasks (Planar-Push too). */
+int mjs_rollout_actor(mjs_handle* h, const mjs_actor* actor, const double* obs0_dev, int32_t T, const mjs_actor_rollout* roll, const mjs_outputs* out,
+                      void* stream);
+
 /* Replaces the Robot entity's control API on a stand-alone UR5e (entities/robots/robot.py:198-272): Robot.moveJ :211-216,
  * Robot.movej_IK :198-209, Robot.servoL :218-225, Robot.servoJ :227-259, then n_substeps x (Robot.before_substep :261-272 +
  * JointTrajectory.get_target_joint_positions joint_trajectory.py:41-47; Physics.step), then Robot.get_tcp_pose :153-168.

@@ -2,7 +2,8 @@
 tlpss/mujoco-sim (physics step + task obs/reward/termination + the dmc2gym step/reset wrapper).
 
 Two front ends over the same C ABI (include/mjsim.h -> libmjsim.so, hand-written HIP):
-  * :class:`HipVectorEnv` — N envs on one GPU, torch tensors in/out (the fast path);
+  * :class:`HipVectorEnv` — N envs on one GPU, torch tensors in/out (the fast path), with :class:`DeviceActor` for a learned
+    MLP policy evaluated on the device;
   * :class:`DMCEnvironmentAdapter` + registry ids — the reference's own single-env gymnasium
     surface (mujoco_sim/__init__.py:19-40, environments/dmc2gym.py:78-168).
 """
@@ -17,6 +18,7 @@ from .environments.tasks.point_reach import PointMassReachTask
 from .environments.tasks.robot_reach import RobotReachConfig, RobotReachTask
 from .environments.tasks.robot_push_button import RobotPushButtonTask
 from .environments.tasks.robot_planar_push import RobotPushConfig, RobotPushTask
+from .policies import DeviceActor  # noqa: F401
 from .recording import LeRobotDatasetRecorder  # noqa: F401
 from .vector_env import TASKS, HipVectorEnv  # noqa: F401
 

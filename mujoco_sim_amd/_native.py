@@ -35,12 +35,16 @@ VARIANT_DEFAULT, VARIANT_SINGLE_WAVE, VARIANT_TWO_ROLES, VARIANT_RESET_GROUPS = 
 UR_STATE = 34
 UR_CMD_NONE, UR_CMD_MOVEJ, UR_CMD_MOVEJ_IK, UR_CMD_SERVOL, UR_CMD_SERVOJ = 0, 1, 2, 3, 4
 UR_EEF_NONE, UR_EEF_GRIPPER = 0, 1
+ACTIVATION_RELU, ACTIVATION_TANH = 0, 1
+ACTOR_VARIANT_DEFAULT, ACTOR_VARIANT_TILE32 = 0, 1
+ACTOR_MAX_IN, ACTOR_MAX_HIDDEN, ACTOR_MAX_LAYERS, ACTOR_MAX_ACTIONS = 64, 256, 3, 8  # the limits mjs_actor_create checks
 
 EXPORTED_SYMBOLS = [
     "mjs_version", "mjs_obs_dim", "mjs_action_dim", "mjs_action_dim_for", "mjs_state_dim", "mjs_env_obs_dim", "mjs_env_state_dim", "mjs_algorithmic_bytes_per_env_step", "mjs_env_algorithmic_bytes_per_env_step", "mjs_substeps",
     "mjs_create", "mjs_destroy", "mjs_last_error", "mjs_seed", "mjs_reset", "mjs_step", "mjs_rollout",
     "mjs_get_state", "mjs_set_state", "mjs_get_rng_state", "mjs_set_rng_state", "mjs_render", "mjs_set_scene_camera", "mjs_get_scene_camera", "mjs_render_rgbd", "mjs_debug_ur5e_ik", "mjs_ur5e_tcp_to_joints", "mjs_ur5e_robot_run",
     "mjs_demonstration_actions", "mjs_rollout_demonstration",
+    "mjs_actor_create", "mjs_actor_destroy", "mjs_actor_load", "mjs_actor_actions", "mjs_rollout_actor",
 ]
 
 
@@ -86,6 +90,34 @@ class MjsDemoRollout(C.Structure):
         super().__init__(*args, **kw)
         if "struct_size" not in kw:
             self.struct_size = C.sizeof(MjsDemoRollout)
+
+
+class _Sized(C.Structure):
+    """A structure whose first field is the struct_size the library validates."""
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        if "struct_size" not in kw:
+            self.struct_size = C.sizeof(type(self))
+
+
+class MjsActorDesc(_Sized):
+    """mjs_actor_desc: the shape of an MLP actor; obs_index is a HOST int32 array (the library copies it)."""
+    _fields_ = [("struct_size", C.c_uint32), ("device", C.c_int32), ("in_dim", C.c_int32), ("n_hidden", C.c_int32), ("hidden", C.c_int32 * 3),
+                ("action_dim", C.c_int32), ("activation", C.c_int32), ("variant", C.c_int32), ("obs_index", C.POINTER(C.c_int32))]
+
+
+class MjsActorWeights(_Sized):
+    """mjs_actor_weights: DEVICE pointers to float32 parameters in torch.nn.Linear layout."""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved0", C.c_int32), ("hidden_w", C.c_void_p * 3), ("hidden_b", C.c_void_p * 3),
+                ("mu_w", C.c_void_p), ("mu_b", C.c_void_p), ("log_std_w", C.c_void_p), ("log_std_b", C.c_void_p)]
+
+
+class MjsActorRollout(_Sized):
+    """mjs_actor_rollout: what a closed-loop actor rollout writes besides MjsOutputs, its noise draws and the action bounds (HOST)."""
+    _fields_ = [("struct_size", C.c_uint32), ("height", C.c_int32), ("width", C.c_int32), ("reserved0", C.c_int32), ("z_dev", C.c_void_p),
+                ("low", C.POINTER(C.c_double)), ("high", C.POINTER(C.c_double)), ("actions_out_dev", C.c_void_p), ("squashed_out_dev", C.c_void_p),
+                ("scene_rgb_dev", C.c_void_p), ("wrist_rgb_dev", C.c_void_p)]
 
 
 class MjsError(RuntimeError):
@@ -196,6 +228,12 @@ def lib() -> C.CDLL:
     L.mjs_render_rgbd.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     L.mjs_demonstration_actions.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]
     L.mjs_rollout_demonstration.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(MjsDemoRollout), C.POINTER(MjsOutputs), C.c_void_p]
+    L.mjs_actor_create.argtypes = [C.POINTER(MjsActorDesc), C.POINTER(C.c_void_p)]
+    L.mjs_actor_destroy.argtypes = [C.c_void_p]
+    L.mjs_actor_destroy.restype = None
+    L.mjs_actor_load.argtypes = [C.c_void_p, C.POINTER(MjsActorWeights), C.c_void_p]
+    L.mjs_actor_actions.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p, C.c_void_p, C.c_void_p]
+    L.mjs_rollout_actor.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(MjsActorRollout), C.POINTER(MjsOutputs), C.c_void_p]
     L.mjs_get_rng_state.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.mjs_set_rng_state.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = L

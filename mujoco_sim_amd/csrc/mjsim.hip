@@ -6,6 +6,7 @@
 #include <memory>
 #include <new>
 #include <string>
+#include <vector>
 
 #include "../../include/mjsim.h"
 #include "mjs_kernel_common.h"
@@ -16,6 +17,7 @@
 #include "mjs_push.h"
 #include "mjs_render.h"
 #include "mjs_policy.h"
+#include "mjs_actor.h"
 #ifdef MJS_STAMPS
 #include "mjs_stamps_report.h"
 #endif
@@ -115,6 +117,19 @@ struct mjs_handle {
   int epoch = 0;               // parity of the next step launch (FLAG_EPOCH)
   double* ws14 = nullptr;      // [bg::WS_DOUBLES][N] constraint rows of the articulated-gripper kernel (mjs_gripper14.h)
   std::string err;
+};
+
+// A learned policy (mjs_actor.h): the shape, and the library's packed copy of the parameters. No per-handle state.
+struct mjs_actor {
+  mjs_actor_desc desc;             // validated; obs_index points at `index`
+  std::vector<int32_t> index;      // host copy of obs_index
+  int max_index = 0;               // the largest obs_index entry: a handle's observation row must be wider
+  int k0 = 0, width[3] = {0, 0, 0};  // in_dim padded to act::KPAD, hidden widths padded to act::OPAD
+  int widest = 0;                  // of k0, width[], act::OPAD: sizes the LDS images
+  int* index_dev = nullptr;
+  float* w[4] = {nullptr, nullptr, nullptr, nullptr};  // packed [k][out]: hidden layers, then (slot 3) the stacked mu / log_std head
+  float* b[4] = {nullptr, nullptr, nullptr, nullptr};
+  bool loaded = false;             // mjs_actor_load has run
 };
 
 namespace {
@@ -456,6 +471,86 @@ const char* policy_refusal(const mjs_handle* h, double noise, int& code) {
   return nullptr;
 }
 
+
+// The closed loop both policy rollouts run (mjs_rollout_demonstration, mjs_rollout_actor): what it writes besides mjs_outputs ...
+struct ClosedLoop {
+  double* actions_out;  // [T, N, action_dim]
+  uint8_t *scene_rgb, *wrist_rgb;
+  int32_t height, width;
+};
+// ... what it refuses (empty = fine; `arg` names the caller's struct in the text) ...
+std::string closed_loop_refusal(const mjs_handle* h, const char* arg, int32_t T, const ClosedLoop& loop, const mjs_outputs* out) {
+  if (T < 0) return "T is negative";
+  if (!out || !out->obs) return "out->obs is required (the policy of step t reads slice t-1)";
+  if (!loop.actions_out) return std::string(arg) + "->actions_out_dev is required";
+  if (loop.wrist_rgb && h->cfg.task != MJS_TASK_BUTTON_PUSH) return "a wrist image buffer on a task without a wrist camera";
+  if ((loop.scene_rgb || loop.wrist_rgb) && (loop.height <= 0 || loop.width <= 0)) return "image buffers need a positive height and width";
+  return "";
+}
+// ... and the loop: policy(t, obs of step t-1, slice t of actions_out) launches the policy of step t; the frames of the state it has
+// just looked at; the ordinary step launch. Arguments validated, the handle's device selected by the caller.
+template <class Policy>
+int closed_loop(mjs_handle* h, const double* obs0, int32_t T, const ClosedLoop& loop, const mjs_outputs* out, hipStream_t stream, Policy policy) {
+  const size_t N = (size_t)h->cfg.num_envs, A = (size_t)h->inst.act_dim, O = (size_t)h->inst.obs_dim;
+  const bool images = loop.scene_rgb || loop.wrist_rgb;
+  const size_t frame = images ? N * (size_t)loop.height * (size_t)loop.width * 3 : 0;
+  for (int32_t t = 0; t < T; t++) {
+    const double* obs = t == 0 ? obs0 : out->obs + (size_t)(t - 1) * N * O;
+    double* actions = loop.actions_out + (size_t)t * N * A;
+    int rc = policy(t, obs, actions);
+    if (rc != MJS_OK) return rc;
+    if (loop.scene_rgb && (rc = mjs_render(h, MJS_CAMERA_SCENE, loop.height, loop.width, loop.scene_rgb + (size_t)t * frame, stream)) != MJS_OK) return rc;
+    if (loop.wrist_rgb && (rc = mjs_render(h, MJS_CAMERA_WRIST, loop.height, loop.width, loop.wrist_rgb + (size_t)t * frame, stream)) != MJS_OK) return rc;
+    const mjs_outputs o = slice_outputs(h, out, t);
+    h->prims_valid = false;
+    rc = launch<false>(h, make_params(h, actions, nullptr, &o), stream);
+    if (rc != MJS_OK) return rc;
+  }
+  return MJS_OK;
+}
+
+
+// what mjs_actor_actions and mjs_rollout_actor refuse about the pair (handle, actor); empty = fine
+std::string actor_refusal(const mjs_handle* h, const mjs_actor* a, const double* low, const double* high) {
+  if (!a) return "actor is null";
+  if (a->desc.device != h->cfg.device) return "the actor lives on another device than the handle";
+  if (!a->loaded) return "the actor has no parameters yet (mjs_actor_load)";
+  if (a->desc.action_dim != h->inst.act_dim) return "the actor's action_dim is not the handle's action width";
+  if (a->max_index >= h->inst.obs_dim) return "an obs_index entry lies outside the handle's observation row (mjs_env_obs_dim)";
+  if (!low || !high) return "low or high is null";
+  return "";
+}
+// one launch of the actor kernel for every env of the handle; arguments validated by the callers
+int launch_actor(mjs_handle* h, const mjs_actor* a, const double* obs, const float* z, const double* low, const double* high, double* actions, float* squashed,
+                 hipStream_t s) {
+  act::ActorParams p;
+  std::memset(&p, 0, sizeof p);
+  p.N = h->cfg.num_envs;
+  p.obs_dim = h->inst.obs_dim;
+  p.in_dim = a->desc.in_dim;
+  p.n_hidden = a->desc.n_hidden;
+  p.A = a->desc.action_dim;
+  p.activation = a->desc.activation == MJS_ACTIVATION_TANH ? act::ACT_TANH : act::ACT_RELU;
+  p.S = act::lds_stride(a->widest);
+  p.k0 = a->k0;
+  p.w0 = a->width[0]; p.w1 = a->width[1]; p.w2 = a->width[2];
+  p.obs_index = a->index_dev;
+  p.W0 = a->w[0]; p.W1 = a->w[1]; p.W2 = a->w[2]; p.WH = a->w[3];
+  p.B0 = a->b[0]; p.B1 = a->b[1]; p.B2 = a->b[2]; p.BH = a->b[3];
+  p.obs = obs;
+  p.z = z;
+  p.actions = actions;
+  p.squashed = squashed;
+  for (int k = 0; k < p.A; k++) { p.low[k] = low[k]; p.high[k] = high[k]; }
+  // 16 envs per workgroup on the 16x16x4 instruction: at 4096 envs that is one workgroup for each of the 256 CUs, where 32-env
+  // tiles leave half of them idle (numbers: DESIGN.md 4, profiles/actor_rollout_timing.txt)
+  if (a->desc.variant == MJS_ACTOR_VARIANT_TILE32)
+    act::kernel<32><<<dim3((unsigned)((p.N + 31) / 32)), act::WAVES * 64, act::lds_bytes(32, a->widest), s>>>(p);
+  else
+    act::kernel<16><<<dim3((unsigned)((p.N + 15) / 16)), act::WAVES * 64, act::lds_bytes(16, a->widest), s>>>(p);
+  HIP_TRY(h, hipGetLastError());
+  return MJS_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -629,41 +724,158 @@ int mjs_demonstration_actions(mjs_handle* h, const double* obs_dev, const double
 }
 
 int mjs_rollout_demonstration(mjs_handle* h, const double* obs0_dev, int32_t T, const mjs_demo_rollout* demo, const mjs_outputs* out, void* stream) {
-  if (!h) return fail(nullptr, MJS_ERR_INVALID_ARG, "mjs_rollout_demonstration: null handle");
-  if (!demo) return fail(h, MJS_ERR_INVALID_ARG, "mjs_rollout_demonstration: demo is null");
+  const std::string name = "mjs_rollout_demonstration";
+  if (!h) return fail(nullptr, MJS_ERR_INVALID_ARG, name + ": null handle");
+  if (!demo) return fail(h, MJS_ERR_INVALID_ARG, name + ": demo is null");
   if (demo->struct_size != sizeof(mjs_demo_rollout))
-    return fail(h, MJS_ERR_INVALID_ARG, "mjs_rollout_demonstration: mjs_demo_rollout.struct_size does not match this library's header");
+    return fail(h, MJS_ERR_INVALID_ARG, name + ": mjs_demo_rollout.struct_size does not match this library's header");
   int code;
-  if (const char* why = policy_refusal(h, demo->noise, code)) return fail(h, code, std::string("mjs_rollout_demonstration: ") + why);
-  if (T < 0) return fail(h, MJS_ERR_INVALID_ARG, "mjs_rollout_demonstration: T is negative");
-  if (!out || !out->obs) return fail(h, MJS_ERR_INVALID_ARG, "mjs_rollout_demonstration: out->obs is required (the policy of step t reads slice t-1)");
-  if (!demo->actions_out_dev) return fail(h, MJS_ERR_INVALID_ARG, "mjs_rollout_demonstration: demo->actions_out_dev is required");
-  if (demo->wrist_rgb_dev && h->cfg.task != MJS_TASK_BUTTON_PUSH)
-    return fail(h, MJS_ERR_INVALID_ARG, "mjs_rollout_demonstration: a wrist image buffer on a task without a wrist camera");
-  const bool images = demo->scene_rgb_dev || demo->wrist_rgb_dev;
-  if (images && (demo->height <= 0 || demo->width <= 0)) return fail(h, MJS_ERR_INVALID_ARG, "mjs_rollout_demonstration: image buffers need a positive height and width");
+  if (const char* why = policy_refusal(h, demo->noise, code)) return fail(h, code, name + ": " + why);
+  const ClosedLoop loop{demo->actions_out_dev, demo->scene_rgb_dev, demo->wrist_rgb_dev, demo->height, demo->width};
+  const std::string why = closed_loop_refusal(h, "demo", T, loop, out);
+  if (!why.empty()) return fail(h, MJS_ERR_INVALID_ARG, name + ": " + why);
   if (T == 0) return MJS_OK;
-  if (!obs0_dev) return fail(h, MJS_ERR_INVALID_ARG, "mjs_rollout_demonstration: obs0_dev is null");
+  if (!obs0_dev) return fail(h, MJS_ERR_INVALID_ARG, name + ": obs0_dev is null");
   DeviceGuard dev_(h->cfg.device);
   HIP_TRY(h, dev_.err);
-  const size_t N = (size_t)h->cfg.num_envs, A = (size_t)h->inst.act_dim, O = (size_t)h->inst.obs_dim;
+  const size_t N = (size_t)h->cfg.num_envs;
   const size_t k = h->cfg.task == MJS_TASK_POINTMASS_REACH ? 2 : 3;  // noise draws per env
-  const size_t frame = images ? N * (size_t)demo->height * (size_t)demo->width * 3 : 0;
-  for (int32_t t = 0; t < T; t++) {
-    const double* obs = t == 0 ? obs0_dev : out->obs + (size_t)(t - 1) * N * O;
-    double* actions = demo->actions_out_dev + (size_t)t * N * A;
-    int rc = launch_policy(h, obs, demo->noise_z_dev ? demo->noise_z_dev + (size_t)t * N * k : nullptr, demo->noise, actions,
-                           demo->ik_ok_dev ? demo->ik_ok_dev + (size_t)t * N : nullptr, (hipStream_t)stream);
-    if (rc != MJS_OK) return rc;
-    // the frames of the state the policy has just looked at
-    if (demo->scene_rgb_dev && (rc = mjs_render(h, MJS_CAMERA_SCENE, demo->height, demo->width, demo->scene_rgb_dev + (size_t)t * frame, stream)) != MJS_OK) return rc;
-    if (demo->wrist_rgb_dev && (rc = mjs_render(h, MJS_CAMERA_WRIST, demo->height, demo->width, demo->wrist_rgb_dev + (size_t)t * frame, stream)) != MJS_OK) return rc;
-    const mjs_outputs o = slice_outputs(h, out, t);
-    h->prims_valid = false;
-    rc = launch<false>(h, make_params(h, actions, nullptr, &o), (hipStream_t)stream);
-    if (rc != MJS_OK) return rc;
+  return closed_loop(h, obs0_dev, T, loop, out, (hipStream_t)stream, [&](int32_t t, const double* obs, double* actions) {
+    return launch_policy(h, obs, demo->noise_z_dev ? demo->noise_z_dev + (size_t)t * N * k : nullptr, demo->noise, actions,
+                         demo->ik_ok_dev ? demo->ik_ok_dev + (size_t)t * N : nullptr, (hipStream_t)stream);
+  });
+}
+
+// ---- learned policies: the MLP actor ------------------------------------------------------------------------------------------
+int mjs_actor_create(const mjs_actor_desc* desc, mjs_actor** out) {
+  if (!desc || !out) return fail(nullptr, MJS_ERR_INVALID_ARG, "mjs_actor_create: null argument");
+  *out = nullptr;
+  if (desc->struct_size != sizeof(mjs_actor_desc))
+    return fail(nullptr, MJS_ERR_INVALID_ARG, "mjs_actor_create: mjs_actor_desc.struct_size does not match this library's header");
+  if (desc->in_dim < 1 || desc->in_dim > act::MAX_IN) return fail(nullptr, MJS_ERR_INVALID_ARG, "mjs_actor_create: in_dim must be 1..64");
+  if (desc->n_hidden < 1 || desc->n_hidden > act::MAX_LAYERS) return fail(nullptr, MJS_ERR_INVALID_ARG, "mjs_actor_create: n_hidden must be 1..3");
+  for (int l = 0; l < desc->n_hidden; l++)
+    if (desc->hidden[l] < 1 || desc->hidden[l] > act::MAX_HIDDEN) return fail(nullptr, MJS_ERR_INVALID_ARG, "mjs_actor_create: every hidden width must be 1..256");
+  if (desc->action_dim < 1 || desc->action_dim > act::MAX_ACT) return fail(nullptr, MJS_ERR_INVALID_ARG, "mjs_actor_create: action_dim must be 1..8");
+  if (desc->activation != MJS_ACTIVATION_RELU && desc->activation != MJS_ACTIVATION_TANH) return fail(nullptr, MJS_ERR_INVALID_ARG, "mjs_actor_create: bad activation");
+  if (desc->variant != MJS_ACTOR_VARIANT_DEFAULT && desc->variant != MJS_ACTOR_VARIANT_TILE32) return fail(nullptr, MJS_ERR_INVALID_ARG, "mjs_actor_create: bad variant");
+  if (!desc->obs_index) return fail(nullptr, MJS_ERR_INVALID_ARG, "mjs_actor_create: obs_index is null");
+  for (int j = 0; j < desc->in_dim; j++)
+    if (desc->obs_index[j] < 0) return fail(nullptr, MJS_ERR_INVALID_ARG, "mjs_actor_create: an obs_index entry is negative");
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+    return fail(nullptr, MJS_ERR_NO_DEVICE, "mjs_actor_create: no HIP device visible (this library has no CPU path)");
+  if (desc->device < 0 || desc->device >= ndev) return fail(nullptr, MJS_ERR_INVALID_ARG, "mjs_actor_create: device ordinal out of range");
+  DeviceGuard dev_(desc->device);
+  std::unique_ptr<mjs_actor, void (*)(mjs_actor*)> guard(new (std::nothrow) mjs_actor(), mjs_actor_destroy);
+  mjs_actor* a = guard.get();
+  if (!a) return fail(nullptr, MJS_ERR_ALLOC, "mjs_actor_create: out of host memory");
+#define ACTOR_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return hip_fail(nullptr, e_, "mjs_actor_create: " #expr); } while (0)
+  ACTOR_TRY(dev_.err);
+  a->desc = *desc;
+  a->index.assign(desc->obs_index, desc->obs_index + desc->in_dim);
+  a->desc.obs_index = a->index.data();
+  for (int32_t v : a->index) a->max_index = v > a->max_index ? v : a->max_index;
+  a->k0 = act::round_up(desc->in_dim, act::KPAD);
+  a->widest = a->k0 > act::OPAD ? a->k0 : act::OPAD;
+  for (int l = 0; l < desc->n_hidden; l++) {
+    a->width[l] = act::round_up(desc->hidden[l], act::OPAD);
+    a->widest = a->width[l] > a->widest ? a->width[l] : a->widest;
   }
+  ACTOR_TRY(hipMalloc(&a->index_dev, sizeof(int32_t) * a->index.size()));
+  ACTOR_TRY(hipMemcpy(a->index_dev, a->index.data(), sizeof(int32_t) * a->index.size(), hipMemcpyHostToDevice));
+  int K = a->k0;
+  for (int l = 0; l < desc->n_hidden; l++) {
+    ACTOR_TRY(hipMalloc(&a->w[l], sizeof(float) * (size_t)K * a->width[l]));
+    ACTOR_TRY(hipMalloc(&a->b[l], sizeof(float) * a->width[l]));
+    K = a->width[l];
+  }
+  ACTOR_TRY(hipMalloc(&a->w[3], sizeof(float) * (size_t)K * act::OPAD));
+  ACTOR_TRY(hipMalloc(&a->b[3], sizeof(float) * act::OPAD));
+  // the two LDS images of the 32-env kernel pass 64 KB from a widest layer of 256 on: an opt-in (gfx950 has 160 KB per CU)
+  static_assert(act::lds_bytes(32, act::MAX_HIDDEN) <= 160 * 1024 && act::lds_bytes(16, act::MAX_HIDDEN) <= 64 * 1024, "LDS images of the actor kernels");
+  if (desc->variant == MJS_ACTOR_VARIANT_TILE32)
+    ACTOR_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&act::kernel<32>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)act::lds_bytes(32, act::MAX_HIDDEN)));
+#undef ACTOR_TRY
+  *out = guard.release();
   return MJS_OK;
+}
+
+void mjs_actor_destroy(mjs_actor* a) {
+  if (!a) return;
+  if (a->index_dev) (void)hipFree(a->index_dev);
+  for (int l = 0; l < 4; l++) {
+    if (a->w[l]) (void)hipFree(a->w[l]);
+    if (a->b[l]) (void)hipFree(a->b[l]);
+  }
+  delete a;
+}
+
+int mjs_actor_load(mjs_actor* a, const mjs_actor_weights* wts, void* stream) {
+  if (!a || !wts) return fail(nullptr, MJS_ERR_INVALID_ARG, "mjs_actor_load: null argument");
+  if (wts->struct_size != sizeof(mjs_actor_weights))
+    return fail(nullptr, MJS_ERR_INVALID_ARG, "mjs_actor_load: mjs_actor_weights.struct_size does not match this library's header");
+  for (int l = 0; l < a->desc.n_hidden; l++)
+    if (!wts->hidden_w[l] || !wts->hidden_b[l]) return fail(nullptr, MJS_ERR_INVALID_ARG, "mjs_actor_load: a hidden layer's weight or bias is null");
+  if (!wts->mu_w || !wts->mu_b || !wts->log_std_w || !wts->log_std_b) return fail(nullptr, MJS_ERR_INVALID_ARG, "mjs_actor_load: a head's weight or bias is null");
+  DeviceGuard dev_(a->desc.device);
+  HIP_TRY(nullptr, dev_.err);
+  int in = a->desc.in_dim, K = a->k0;
+  for (int l = 0; l <= a->desc.n_hidden; l++) {
+    const bool head = l == a->desc.n_hidden;
+    act::PackParams p;
+    p.w0 = head ? wts->mu_w : wts->hidden_w[l];
+    p.b0 = head ? wts->mu_b : wts->hidden_b[l];
+    p.w1 = head ? wts->log_std_w : nullptr;
+    p.b1 = head ? wts->log_std_b : nullptr;
+    p.out0 = head ? a->desc.action_dim : a->desc.hidden[l];
+    p.out1 = head ? a->desc.action_dim : 0;
+    p.in = in;
+    p.K = K;
+    p.O = head ? act::OPAD : a->width[l];
+    p.dst_w = a->w[head ? 3 : l];
+    p.dst_b = a->b[head ? 3 : l];
+    act::pack_kernel<<<dim3((unsigned)((p.K * p.O + 255) / 256)), 256, 0, (hipStream_t)stream>>>(p);
+    if (!head) { in = a->desc.hidden[l]; K = a->width[l]; }
+  }
+  HIP_TRY(nullptr, hipGetLastError());
+  a->loaded = true;
+  return MJS_OK;
+}
+
+int mjs_actor_actions(mjs_handle* h, const mjs_actor* actor, const double* obs_dev, const float* z_dev, const double* low, const double* high,
+                      double* actions_dev, float* squashed_out_dev, void* stream) {
+  const std::string name = "mjs_actor_actions";
+  if (!h) return fail(nullptr, MJS_ERR_INVALID_ARG, name + ": null handle");
+  const std::string why = actor_refusal(h, actor, low, high);
+  if (!why.empty()) return fail(h, MJS_ERR_INVALID_ARG, name + ": " + why);
+  if (!obs_dev || !actions_dev) return fail(h, MJS_ERR_INVALID_ARG, name + ": obs_dev or actions_dev is null");
+  DeviceGuard dev_(h->cfg.device);
+  HIP_TRY(h, dev_.err);
+  return launch_actor(h, actor, obs_dev, z_dev, low, high, actions_dev, squashed_out_dev, (hipStream_t)stream);
+}
+
+int mjs_rollout_actor(mjs_handle* h, const mjs_actor* actor, const double* obs0_dev, int32_t T, const mjs_actor_rollout* roll, const mjs_outputs* out,
+                      void* stream) {
+  const std::string name = "mjs_rollout_actor";
+  if (!h) return fail(nullptr, MJS_ERR_INVALID_ARG, name + ": null handle");
+  if (!roll) return fail(h, MJS_ERR_INVALID_ARG, name + ": roll is null");
+  if (roll->struct_size != sizeof(mjs_actor_rollout))
+    return fail(h, MJS_ERR_INVALID_ARG, name + ": mjs_actor_rollout.struct_size does not match this library's header");
+  std::string why = actor_refusal(h, actor, roll->low, roll->high);
+  if (!why.empty()) return fail(h, MJS_ERR_INVALID_ARG, name + ": " + why);
+  const ClosedLoop loop{roll->actions_out_dev, roll->scene_rgb_dev, roll->wrist_rgb_dev, roll->height, roll->width};
+  why = closed_loop_refusal(h, "roll", T, loop, out);
+  if (!why.empty()) return fail(h, MJS_ERR_INVALID_ARG, name + ": " + why);
+  if (T == 0) return MJS_OK;
+  if (!obs0_dev) return fail(h, MJS_ERR_INVALID_ARG, name + ": obs0_dev is null");
+  DeviceGuard dev_(h->cfg.device);
+  HIP_TRY(h, dev_.err);
+  const size_t NA = (size_t)h->cfg.num_envs * (size_t)h->inst.act_dim;
+  return closed_loop(h, obs0_dev, T, loop, out, (hipStream_t)stream, [&](int32_t t, const double* obs, double* actions) {
+    return launch_actor(h, actor, obs, roll->z_dev ? roll->z_dev + (size_t)t * NA : nullptr, roll->low, roll->high, actions,
+                        roll->squashed_out_dev ? roll->squashed_out_dev + (size_t)t * NA : nullptr, (hipStream_t)stream);
+  });
 }
 
 // ---- cameras ------------------------------------------------------------------------------------------------------------

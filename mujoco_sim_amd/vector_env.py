@@ -406,6 +406,82 @@ class HipVectorEnv:
         res.update(images)
         return res
 
+    # ------------------------------------------------------------------ learned policies on the device (policies.DeviceActor)
+    def _action_bounds(self):
+        """(low, high) of the action space as HOST float64 arrays, the form the actor entry points take."""
+        if getattr(self, "_bounds", None) is None:
+            A = self.action_dim
+            self._bounds = ((C.c_double * A)(*map(float, self.action_low)), (C.c_double * A)(*map(float, self.action_high)))
+        return self._bounds
+
+    def _actor_z(self, deterministic, generator, z, lead=()):
+        shape = (*lead, self.num_envs, self.action_dim)
+        if deterministic:
+            if z is not None:
+                raise ValueError("deterministic actions take no draws z")
+            return None
+        if z is not None:
+            if tuple(z.shape) != shape or z.dtype != torch.float32 or z.device != self.device or not z.is_contiguous():
+                raise ValueError(f"z must be a contiguous float32 tensor of shape {shape} on {self.device}")
+            return z
+        return torch.randn(*lead, self.num_envs, self.action_dim, dtype=torch.float32, device=self.device, generator=generator)
+
+    def actor_actions(self, actor, deterministic: bool = False, generator: torch.Generator | None = None, out: torch.Tensor | None = None,
+                      z: torch.Tensor | None = None):
+        """A :class:`~mujoco_sim_amd.policies.DeviceActor` (SAC's MLP actor) for every env, from ``flat_obs``, in ONE launch:
+        ``(actions [N, A] float64, squashed [N, A] float32)``. ``squashed`` = tanh(mu + exp(log_std) * z) (or tanh(mu) with
+        ``deterministic``) is what SB3 stores in a replay buffer; ``actions`` is its affine image in the action space
+        (SB3's ``unscale_action``, in float64), ready for :meth:`step`. The standard-normal draws ``z`` come from
+        ``torch.randn(N, A, dtype=float32, generator=generator)`` on the device, or are the caller's ``z`` (float32 [N, A]).
+        ``out``: the action buffer to write."""
+        if out is None:
+            out = torch.empty(self.num_envs, self.action_dim, dtype=torch.float64, device=self.device)
+        assert out.shape == (self.num_envs, self.action_dim) and out.dtype == torch.float64 and out.is_contiguous()
+        squashed = torch.empty(self.num_envs, self.action_dim, dtype=torch.float32, device=self.device)
+        z = self._actor_z(deterministic, generator, z)
+        low, high = self._action_bounds()
+        nat.check(self._lib.mjs_actor_actions(self._h, actor._a, self._buf["obs"].data_ptr(), z.data_ptr() if z is not None else None, low, high,
+                                              out.data_ptr(), squashed.data_ptr(), self._stream()), self._h)
+        return out, squashed
+
+    def actor_rollout(self, actor, T: int, deterministic: bool = False, generator: torch.Generator | None = None, render: bool = False,
+                      keep: tuple = ("obs", "reward", "terminated", "truncated", "is_success", "step_type", "fault", "ncon", "discount"),
+                      z: torch.Tensor | None = None):
+        """T closed-loop control steps under a :class:`~mujoco_sim_amd.policies.DeviceActor` without returning to Python: per step
+        the actor launch (it reads the previous step's observation; ``flat_obs`` for the first) and the ordinary step launch.
+        Returns :meth:`demonstration_rollout`'s dict with ``"squashed_actions"`` [T, N, A] float32 in place of ``"ik_ok"``;
+        ``LeRobotDatasetRecorder.record_rollout`` takes it unchanged. Equal, bit for bit, to T x (``actor_actions``; ``step``)
+        with the same draws (``z``: float32 [T, N, A], slice t for step t; default ``torch.randn(T, N, A, generator=generator)``).
+        Afterwards ``flat_obs`` holds the block's last observation, so that calls chain."""
+        T = int(T)
+        if T < 0:
+            raise ValueError("T must not be negative")
+        N, dev = self.num_envs, self.device
+        keep = tuple(keep) + ("obs",)  # step t's actor reads slice t-1
+        buf = {k: (torch.zeros((T,) + tuple(v.shape), dtype=v.dtype, device=dev) if k in keep else None) for k, v in self._buf.items()}
+        actions = torch.zeros(T, N, self.action_dim, dtype=torch.float64, device=dev)
+        squashed = torch.zeros(T, N, self.action_dim, dtype=torch.float32, device=dev)
+        z = self._actor_z(deterministic, generator, z, lead=(T,))
+        images = {}
+        if render:
+            r = self.image_resolution
+            if self.use_wrist_camera:
+                images["ur5e/Camera/rgb_image"] = torch.zeros(T, N, r, r, 3, dtype=torch.uint8, device=dev)
+            images["Camera/rgb_image"] = torch.zeros(T, N, r, r, 3, dtype=torch.uint8, device=dev)
+        if T:  # (an empty block needs no launch, and empty tensors have no address to pass)
+            ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+            low, high = self._action_bounds()
+            roll = nat.MjsActorRollout(height=self.image_resolution, width=self.image_resolution, z_dev=ptr(z), low=low, high=high,
+                                       actions_out_dev=actions.data_ptr(), squashed_out_dev=squashed.data_ptr(),
+                                       scene_rgb_dev=ptr(images.get("Camera/rgb_image")), wrist_rgb_dev=ptr(images.get("ur5e/Camera/rgb_image")))
+            out = self._make_outputs(buf)
+            nat.check(self._lib.mjs_rollout_actor(self._h, actor._a, self._buf["obs"].data_ptr(), T, C.byref(roll), C.byref(out), self._stream()), self._h)
+            self._buf["obs"].copy_(buf["obs"][-1])
+        res = {k: v for k, v in buf.items() if v is not None}
+        res["actions"], res["squashed_actions"] = actions, squashed
+        res.update(images)
+        return res
+
     @property
     def flat_observation_layout(self) -> tuple:
         """((key, start, length), ...) of the state keys of this handle's observation dict inside a ``flat_obs`` row."""
