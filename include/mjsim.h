@@ -345,6 +345,90 @@ typedef struct {
 int mjs_rollout_actor(mjs_handle* h, const mjs_actor* actor, const double* obs0_dev, int32_t T, const mjs_actor_rollout* roll, const mjs_outputs* out,
                       void* stream);
 
+/* The image encoder of a visual policy on the device (entry points added after abi 3; mjs_config and the number stay as they are):
+ * SB3's NatureCNN (stable_baselines3/common/torch_layers.py), what MultiInputPolicy's CombinedExtractor puts between every camera
+ * image and the actor above in the reference's RL scripts (scripts/sb3/reach_sac.py, planar_push.py, sb3_sac.py: observation_type
+ * VISUAL_OBS), evaluated on the frames mjs_render writes (csrc/mjs_encoder.h), in float32 with float32 accumulation:
+ *   x[c][y][x] = (float) rgb[n][y][x][c] / 255.0f      conv1 3->32 8x8 stride 4, conv2 32->64 4x4 stride 2, conv3 64->64 3x3 stride 1,
+ *   no padding, ReLU after each; flat = conv3's output in CHW order; features = ReLU(W_fc flat + b_fc).
+ * An encoder belongs to a device and an image size, not to a handle. */
+typedef struct mjs_encoder mjs_encoder;
+typedef struct {
+  uint32_t struct_size;      /* sizeof(mjs_encoder_desc), validated like mjs_config's */
+  int32_t device;            /* HIP device ordinal */
+  int32_t height, width;     /* of the frames: each 36..96 (36 is NatureCNN's own minimum), need not be equal */
+  int32_t channels;          /* 3 */
+  int32_t features_dim;      /* F: 1..512 */
+} mjs_encoder_desc;          /* 24 bytes */
+/* Allocates the packed weight buffers and nothing else. MJS_ERR_INVALID_ARG (text in mjs_last_error(NULL)) for a wrong struct_size, a
+ * null pointer or any field out of range. */
+int mjs_encoder_create(const mjs_encoder_desc* desc, mjs_encoder** out);
+void mjs_encoder_destroy(mjs_encoder* enc);
+/* DEVICE pointers to float32 parameters in torch layout: Conv2d weight [out, in, kh, kw], Linear weight [F, n_flatten], biases [out]. */
+typedef struct {
+  uint32_t struct_size;      /* sizeof(mjs_encoder_weights) */
+  int32_t reserved0;         /* 0 */
+  const float *conv1_w, *conv1_b;  /* [32, 3, 8, 8], [32] */
+  const float *conv2_w, *conv2_b;  /* [64, 32, 4, 4], [64] */
+  const float *conv3_w, *conv3_b;  /* [64, 64, 3, 3], [64] */
+  const float *fc_w, *fc_b;        /* [F, mjs_encoder_flat_dim], [F] */
+} mjs_encoder_weights;       /* 72 bytes */
+/* Packs the parameters into the encoder's own K-major copy with small kernels on the caller's stream; never synchronises
+ * (mjs_actor_load's contract). */
+int mjs_encoder_load(mjs_encoder* enc, const mjs_encoder_weights* weights, void* stream);
+/* n_flatten = 64 * H3 * W3, the width of the linear layer's input (negative: enc is NULL) */
+int mjs_encoder_flat_dim(const mjs_encoder* enc);
+/* bytes of the workspace mjs_encoder_features needs for n images (conv3's output, float32 [n, n_flatten]); 0 for a bad argument */
+uint64_t mjs_encoder_workspace_bytes(const mjs_encoder* enc, int32_t n);
+/* Two launches: rgb_dev uint8 [n, height, width, 3] -> features_dev float32 [n, F]. workspace_dev: mjs_encoder_workspace_bytes(enc, n)
+ * bytes, 16-byte aligned, overwritten. No handle; the launches go to the encoder's device. MJS_ERR_INVALID_ARG (nothing launched) for
+ * a null pointer, n < 0 or an encoder that was never loaded; n == 0 does nothing and returns 0. */
+int mjs_encoder_features(const mjs_encoder* enc, const uint8_t* rgb_dev, int32_t n, void* workspace_dev, float* features_dev, void* stream);
+
+/* A visual actor: the MLP actor above whose input vector is a concatenation of observation columns (desc->in_dim of them, 0..64, in
+ * obs_index order) and up to two float32 feature blocks [N, width] from encoders. Slot 0 is the scene camera's block, slot 1 the
+ * wrist camera's (Button-Push); a slot of width 0 is absent. start[s] is the position of the block's first component in the input
+ * vector; the observation columns fill the positions the blocks leave, in order. The first layer's weight is
+ * [hidden[0], in_dim + width[0] + width[1]]. */
+typedef struct {
+  uint32_t struct_size;      /* sizeof(mjs_actor_feature_inputs) */
+  int32_t n_blocks;          /* 1..2: the number of slots with a positive width */
+  int32_t width[2];          /* 0 (absent) or 1..512 */
+  int32_t start[2];          /* 0..in_dim + the other block's width; blocks must not overlap */
+} mjs_actor_feature_inputs;  /* 24 bytes */
+/* mjs_actor_create for a visual actor. desc as there, except that in_dim may be 0 (obs_index is then ignored) and variant must be
+ * MJS_ACTOR_VARIANT_DEFAULT. Such an actor is refused by mjs_actor_actions / mjs_rollout_actor, and an actor of mjs_actor_create by
+ * the two entry points below; mjs_actor_load and mjs_actor_destroy serve both. */
+int mjs_actor_create_visual(const mjs_actor_desc* desc, const mjs_actor_feature_inputs* blocks, mjs_actor** out);
+/* mjs_actor_actions with the feature blocks: features_dev[s] float32 [N, width[s]] for every slot the actor has (others ignored). */
+int mjs_actor_actions_visual(mjs_handle* h, const mjs_actor* actor, const double* obs_dev, const float* const features_dev[2], const float* z_dev,
+                             const double* low, const double* high, double* actions_dev, float* squashed_out_dev, void* stream);
+typedef struct {
+  uint32_t struct_size;        /* sizeof(mjs_visual_rollout) */
+  int32_t reserved0;           /* 0 */
+  const float* z_dev;          /* [T, N, action_dim] or NULL (deterministic) */
+  const double* low;           /* HOST [action_dim] */
+  const double* high;          /* HOST [action_dim] */
+  double* actions_out_dev;     /* [T, N, action_dim], required */
+  float* squashed_out_dev;     /* [T, N, action_dim] or NULL */
+  uint8_t* scene_rgb_dev;      /* [T, N, H, W, 3] or NULL; H x W are the encoders' */
+  uint8_t* wrist_rgb_dev;      /* the same for MJS_CAMERA_WRIST (Button-Push only) */
+  uint8_t* scene_scratch_dev;  /* [N, H, W, 3]: one step's frame of a camera the actor uses; required where its [T, ...] buffer is NULL */
+  uint8_t* wrist_scratch_dev;
+  float* features_dev[2];      /* [N, width[s]]: required for every slot the actor has; overwritten at every step */
+  void* workspace_dev;         /* required: the largest mjs_encoder_workspace_bytes(enc[s], N) of the encoders given */
+} mjs_visual_rollout;          /* 104 bytes */
+/* mjs_rollout_actor for a visual actor: enc[0] encodes the scene camera, enc[1] the wrist camera, given exactly for the slots the
+ * actor has; both of one image size. Per control step t, in order: the cameras the actor uses (and those with a [T, ...] buffer) are
+ * rendered at the encoders' H x W (the launches of mjs_render; slice t = the frame BEFORE the action); the encoders run
+ * (mjs_encoder_features); the actor launch reads slice t-1 of out->obs (obs0_dev for t = 0) and the feature blocks; the ordinary step
+ * launch writes slice t of out. Refusals (nothing launched, text in mjs_last_error): those of mjs_rollout_actor; an encoder of another
+ * device; an encoder never loaded; an encoder whose F is not the actor's block width, or missing or surplus for a slot; encoders of
+ * two image sizes; a wrist encoder or buffer on a task without a wrist camera; a null workspace, feature buffer or required
+ * scratch. T == 0 does nothing and returns 0. All four tasks, whatever the handle's observation settings. */
+int mjs_rollout_visual_actor(mjs_handle* h, const mjs_actor* actor, mjs_encoder* const enc[2], const double* obs0_dev, int32_t T,
+                             const mjs_visual_rollout* roll, const mjs_outputs* out, void* stream);
+
 /* Replaces the Robot entity's control API on a stand-alone UR5e (entities/robots/robot.py:198-272): Robot.moveJ :211-216,
  * Robot.movej_IK :198-209, Robot.servoL :218-225, Robot.servoJ :227-259, then n_substeps x (Robot.before_substep :261-272 +
  * JointTrajectory.get_target_joint_positions joint_trajectory.py:41-47; Physics.step), then Robot.get_tcp_pose :153-168.

@@ -38,6 +38,7 @@ UR_EEF_NONE, UR_EEF_GRIPPER = 0, 1
 ACTIVATION_RELU, ACTIVATION_TANH = 0, 1
 ACTOR_VARIANT_DEFAULT, ACTOR_VARIANT_TILE32 = 0, 1
 ACTOR_MAX_IN, ACTOR_MAX_HIDDEN, ACTOR_MAX_LAYERS, ACTOR_MAX_ACTIONS = 64, 256, 3, 8  # the limits mjs_actor_create checks
+ENCODER_MIN_SIZE, ENCODER_MAX_SIZE, ENCODER_MAX_FEATURES, ACTOR_MAX_BLOCKS = 36, 96, 512, 2  # the limits mjs_encoder_create / mjs_actor_create_visual check
 
 EXPORTED_SYMBOLS = [
     "mjs_version", "mjs_obs_dim", "mjs_action_dim", "mjs_action_dim_for", "mjs_state_dim", "mjs_env_obs_dim", "mjs_env_state_dim", "mjs_algorithmic_bytes_per_env_step", "mjs_env_algorithmic_bytes_per_env_step", "mjs_substeps",
@@ -45,6 +46,8 @@ EXPORTED_SYMBOLS = [
     "mjs_get_state", "mjs_set_state", "mjs_get_rng_state", "mjs_set_rng_state", "mjs_render", "mjs_set_scene_camera", "mjs_get_scene_camera", "mjs_render_rgbd", "mjs_debug_ur5e_ik", "mjs_ur5e_tcp_to_joints", "mjs_ur5e_robot_run",
     "mjs_demonstration_actions", "mjs_rollout_demonstration",
     "mjs_actor_create", "mjs_actor_destroy", "mjs_actor_load", "mjs_actor_actions", "mjs_rollout_actor",
+    "mjs_encoder_create", "mjs_encoder_destroy", "mjs_encoder_load", "mjs_encoder_flat_dim", "mjs_encoder_workspace_bytes", "mjs_encoder_features",
+    "mjs_actor_create_visual", "mjs_actor_actions_visual", "mjs_rollout_visual_actor",
 ]
 
 
@@ -118,6 +121,30 @@ class MjsActorRollout(_Sized):
     _fields_ = [("struct_size", C.c_uint32), ("height", C.c_int32), ("width", C.c_int32), ("reserved0", C.c_int32), ("z_dev", C.c_void_p),
                 ("low", C.POINTER(C.c_double)), ("high", C.POINTER(C.c_double)), ("actions_out_dev", C.c_void_p), ("squashed_out_dev", C.c_void_p),
                 ("scene_rgb_dev", C.c_void_p), ("wrist_rgb_dev", C.c_void_p)]
+
+
+class MjsEncoderDesc(_Sized):
+    """mjs_encoder_desc: the image size and feature width of a NatureCNN encoder."""
+    _fields_ = [("struct_size", C.c_uint32), ("device", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("channels", C.c_int32),
+                ("features_dim", C.c_int32)]
+
+
+class MjsEncoderWeights(_Sized):
+    """mjs_encoder_weights: DEVICE pointers to float32 parameters in torch layout (Conv2d [out, in, kh, kw], Linear [F, n_flatten])."""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved0", C.c_int32), ("conv1_w", C.c_void_p), ("conv1_b", C.c_void_p), ("conv2_w", C.c_void_p),
+                ("conv2_b", C.c_void_p), ("conv3_w", C.c_void_p), ("conv3_b", C.c_void_p), ("fc_w", C.c_void_p), ("fc_b", C.c_void_p)]
+
+
+class MjsActorFeatureInputs(_Sized):
+    """mjs_actor_feature_inputs: the feature blocks of a visual actor (slot 0: scene camera, slot 1: wrist camera; width 0: absent)."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_blocks", C.c_int32), ("width", C.c_int32 * 2), ("start", C.c_int32 * 2)]
+
+
+class MjsVisualRollout(_Sized):
+    """mjs_visual_rollout: what a closed-loop visual-actor rollout writes besides MjsOutputs, its draws, bounds (HOST) and scratch."""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved0", C.c_int32), ("z_dev", C.c_void_p), ("low", C.POINTER(C.c_double)), ("high", C.POINTER(C.c_double)),
+                ("actions_out_dev", C.c_void_p), ("squashed_out_dev", C.c_void_p), ("scene_rgb_dev", C.c_void_p), ("wrist_rgb_dev", C.c_void_p),
+                ("scene_scratch_dev", C.c_void_p), ("wrist_scratch_dev", C.c_void_p), ("features_dev", C.c_void_p * 2), ("workspace_dev", C.c_void_p)]
 
 
 class MjsError(RuntimeError):
@@ -234,6 +261,19 @@ def lib() -> C.CDLL:
     L.mjs_actor_load.argtypes = [C.c_void_p, C.POINTER(MjsActorWeights), C.c_void_p]
     L.mjs_actor_actions.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p, C.c_void_p, C.c_void_p]
     L.mjs_rollout_actor.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(MjsActorRollout), C.POINTER(MjsOutputs), C.c_void_p]
+    L.mjs_encoder_create.argtypes = [C.POINTER(MjsEncoderDesc), C.POINTER(C.c_void_p)]
+    L.mjs_encoder_destroy.argtypes = [C.c_void_p]
+    L.mjs_encoder_destroy.restype = None
+    L.mjs_encoder_load.argtypes = [C.c_void_p, C.POINTER(MjsEncoderWeights), C.c_void_p]
+    L.mjs_encoder_flat_dim.argtypes = [C.c_void_p]
+    L.mjs_encoder_workspace_bytes.argtypes = [C.c_void_p, C.c_int32]
+    L.mjs_encoder_workspace_bytes.restype = C.c_uint64
+    L.mjs_encoder_features.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.mjs_actor_create_visual.argtypes = [C.POINTER(MjsActorDesc), C.POINTER(MjsActorFeatureInputs), C.POINTER(C.c_void_p)]
+    L.mjs_actor_actions_visual.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p * 2), C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                           C.c_void_p, C.c_void_p, C.c_void_p]
+    L.mjs_rollout_visual_actor.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p * 2), C.c_void_p, C.c_int32, C.POINTER(MjsVisualRollout), C.POINTER(MjsOutputs),
+                                           C.c_void_p]
     L.mjs_get_rng_state.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.mjs_set_rng_state.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = L

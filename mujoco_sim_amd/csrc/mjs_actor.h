@@ -185,6 +185,93 @@ __global__ __launch_bounds__(WAVES * 64) void kernel(ActorParams p) {
   }
 }
 
+// Feature blocks of a visual actor (mjs_encoder.h): float32 [N, width[s]] per slot (0: scene camera, 1: wrist camera). There, entry j of
+// ActorParams::obs_index is an observation column (>= 0) or -(1 + MAX_BLOCK_WIDTH s + f): component f of slot s.
+constexpr int MAX_BLOCKS = 2, MAX_BLOCK_WIDTH = 512;
+struct FeatureInputs {
+  const float* feat[MAX_BLOCKS];
+  int width[MAX_BLOCKS];
+};
+
+// The visual actor: kernel<16> line for line, except for where x comes from (a kernel of its own, so that the state actor's
+// instantiations stay the instructions they are). in_dim and k0 count the feature blocks (k0 up to 64 + 2 * 512: the LDS images
+// can pass 64 KB, an opt-in). grid = ceil(N / 16).
+__global__ __launch_bounds__(WAVES * 64) void kernel_visual(ActorParams p, FeatureInputs fi) {
+  constexpr int TE = 16;
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int S = p.S;
+  float* buf0 = lds;
+  float* buf1 = lds + TE * S;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int env0 = blockIdx.x * TE;
+
+  // x: observation columns (float64 -> float32, round to nearest) and feature components; rows of envs past N and the k padding are zero
+  for (int e = tid; e < TE * p.k0; e += WAVES * 64) {
+    const int r = e / p.k0, j = e - r * p.k0;
+    float x = 0.0f;
+    if (env0 + r < p.N && j < p.in_dim) {
+      const int c = p.obs_index[j];
+      if (c >= 0) {
+        x = (float)p.obs[(size_t)(env0 + r) * p.obs_dim + c];
+      } else {
+        const int t = -1 - c, slot = t / MAX_BLOCK_WIDTH, f = t - slot * MAX_BLOCK_WIDTH;
+        x = slot == 0 ? fi.feat[0][(size_t)(env0 + r) * fi.width[0] + f] : fi.feat[1][(size_t)(env0 + r) * fi.width[1] + f];
+      }
+    }
+    buf0[r * S + j] = x;
+  }
+  __syncthreads();
+
+  // hidden layers (the launch's layer count is uniform), then the stacked head: mu in columns 0..A-1, log_std in A..2A-1
+  layer<TE, true>(buf0, buf1, S, p.W0, p.B0, p.k0, p.w0, p.activation, wave, lane);
+  __syncthreads();
+  const float* h = buf1;
+  float* other = buf0;
+  int K = p.w0;
+  if (p.n_hidden > 1) {
+    layer<TE, true>(buf1, buf0, S, p.W1, p.B1, p.w0, p.w1, p.activation, wave, lane);
+    __syncthreads();
+    h = buf0; other = buf1; K = p.w1;
+    if (p.n_hidden > 2) {
+      layer<TE, true>(buf0, buf1, S, p.W2, p.B2, p.w1, p.w2, p.activation, wave, lane);
+      __syncthreads();
+      h = buf1; other = buf0; K = p.w2;
+    }
+  }
+  layer<TE, false>(h, other, S, p.WH, p.BH, K, OPAD, p.activation, wave, lane);
+  __syncthreads();
+
+  // one thread per (env, action component)
+  const int A = p.A;
+  if (tid < TE * A) {
+    const int r = tid / A, j = tid - r * A, i = env0 + r;
+    if (i < p.N) {
+      const float mu = other[r * S + j];
+      const float ls = fminf(fmaxf(other[r * S + A + j], LOG_STD_MIN), LOG_STD_MAX);
+      float u = mu;
+      if (p.z) u = mu + expf(ls) * p.z[(size_t)i * A + j];
+      const float a = tanhf(u);
+      if (p.squashed) p.squashed[(size_t)i * A + j] = a;
+      double lo = p.low[0], hi = p.high[0];  // (a select chain: no indexed copy of the argument arrays)
+#pragma unroll
+      for (int k = 1; k < MAX_ACT; k++) {
+        lo = j == k ? p.low[k] : lo;
+        hi = j == k ? p.high[k] : hi;
+      }
+      {
+        // SB3's unscale_action, low + (0.5 * (a + 1.0) * (high - low)), operation by operation in float64: no contraction, so that
+        // the result is the one numpy / torch give for the stored squashed action
+#pragma clang fp contract(off)
+        const double t = (double)a + 1.0;
+        const double half = 0.5 * t;
+        const double span = hi - lo;
+        const double scaled = half * span;
+        p.actions[(size_t)i * A + j] = lo + scaled;
+      }
+    }
+  }
+}
+
 // torch.nn.Linear parameters (weight [out, in] row-major, bias [out]) -> the packed copy: dst_w [K][O], dst_b [O], K >= in, O >= out0 +
 // out1, zero-padded. Two sources stack along the output index (the head: mu, then log_std); src1 nullptr: one source.
 struct PackParams {

@@ -18,6 +18,7 @@
 #include "mjs_render.h"
 #include "mjs_policy.h"
 #include "mjs_actor.h"
+#include "mjs_encoder.h"
 #ifdef MJS_STAMPS
 #include "mjs_stamps_report.h"
 #endif
@@ -130,6 +131,21 @@ struct mjs_actor {
   float* w[4] = {nullptr, nullptr, nullptr, nullptr};  // packed [k][out]: hidden layers, then (slot 3) the stacked mu / log_std head
   float* b[4] = {nullptr, nullptr, nullptr, nullptr};
   bool loaded = false;             // mjs_actor_load has run
+  // a visual actor (mjs_actor_create_visual): feature blocks among the first layer's inputs. `index` then has in_total entries in
+  // act::FeatureInputs' encoding
+  bool visual = false;
+  int in_total = 0;                // desc.in_dim + the blocks' widths: the first layer's fan-in
+  int block_width[act::MAX_BLOCKS] = {0, 0};
+};
+
+// An image encoder (mjs_encoder.h): the geometry, and the library's packed copy of the parameters. No per-handle state.
+struct mjs_encoder {
+  mjs_encoder_desc desc;
+  enc::Geometry g;
+  int Fp = 0;                      // features_dim padded to enc::FPAD
+  float* w[4] = {nullptr, nullptr, nullptr, nullptr};  // packed [k][out]: conv1..3, fc
+  float* b[4] = {nullptr, nullptr, nullptr, nullptr};
+  bool loaded = false;
 };
 
 namespace {
@@ -511,8 +527,11 @@ int closed_loop(mjs_handle* h, const double* obs0, int32_t T, const ClosedLoop& 
 
 
 // what mjs_actor_actions and mjs_rollout_actor refuse about the pair (handle, actor); empty = fine
-std::string actor_refusal(const mjs_handle* h, const mjs_actor* a, const double* low, const double* high) {
+std::string actor_refusal(const mjs_handle* h, const mjs_actor* a, const double* low, const double* high, bool visual = false) {
   if (!a) return "actor is null";
+  if (a->visual != visual)
+    return visual ? "the actor has no feature blocks (mjs_actor_create): use mjs_actor_actions / mjs_rollout_actor"
+                  : "the actor reads feature blocks (mjs_actor_create_visual): use mjs_actor_actions_visual / mjs_rollout_visual_actor";
   if (a->desc.device != h->cfg.device) return "the actor lives on another device than the handle";
   if (!a->loaded) return "the actor has no parameters yet (mjs_actor_load)";
   if (a->desc.action_dim != h->inst.act_dim) return "the actor's action_dim is not the handle's action width";
@@ -522,12 +541,12 @@ std::string actor_refusal(const mjs_handle* h, const mjs_actor* a, const double*
 }
 // one launch of the actor kernel for every env of the handle; arguments validated by the callers
 int launch_actor(mjs_handle* h, const mjs_actor* a, const double* obs, const float* z, const double* low, const double* high, double* actions, float* squashed,
-                 hipStream_t s) {
+                 hipStream_t s, const float* const* features = nullptr) {
   act::ActorParams p;
   std::memset(&p, 0, sizeof p);
   p.N = h->cfg.num_envs;
   p.obs_dim = h->inst.obs_dim;
-  p.in_dim = a->desc.in_dim;
+  p.in_dim = a->in_total;
   p.n_hidden = a->desc.n_hidden;
   p.A = a->desc.action_dim;
   p.activation = a->desc.activation == MJS_ACTIVATION_TANH ? act::ACT_TANH : act::ACT_RELU;
@@ -544,7 +563,11 @@ int launch_actor(mjs_handle* h, const mjs_actor* a, const double* obs, const flo
   for (int k = 0; k < p.A; k++) { p.low[k] = low[k]; p.high[k] = high[k]; }
   // 16 envs per workgroup on the 16x16x4 instruction: at 4096 envs that is one workgroup for each of the 256 CUs, where 32-env
   // tiles leave half of them idle (numbers: DESIGN.md 4, profiles/actor_rollout_timing.txt)
-  if (a->desc.variant == MJS_ACTOR_VARIANT_TILE32)
+  if (a->visual) {
+    act::FeatureInputs fi;
+    for (int b = 0; b < act::MAX_BLOCKS; b++) { fi.feat[b] = a->block_width[b] ? features[b] : nullptr; fi.width[b] = a->block_width[b]; }
+    act::kernel_visual<<<dim3((unsigned)((p.N + 15) / 16)), act::WAVES * 64, act::lds_bytes(16, a->widest), s>>>(p, fi);
+  } else if (a->desc.variant == MJS_ACTOR_VARIANT_TILE32)
     act::kernel<32><<<dim3((unsigned)((p.N + 31) / 32)), act::WAVES * 64, act::lds_bytes(32, a->widest), s>>>(p);
   else
     act::kernel<16><<<dim3((unsigned)((p.N + 15) / 16)), act::WAVES * 64, act::lds_bytes(16, a->widest), s>>>(p);
@@ -747,36 +770,73 @@ int mjs_rollout_demonstration(mjs_handle* h, const double* obs0_dev, int32_t T, 
 }
 
 // ---- learned policies: the MLP actor ------------------------------------------------------------------------------------------
-int mjs_actor_create(const mjs_actor_desc* desc, mjs_actor** out) {
-  if (!desc || !out) return fail(nullptr, MJS_ERR_INVALID_ARG, "mjs_actor_create: null argument");
+// mjs_actor_create (blocks nullptr) and mjs_actor_create_visual
+static int actor_create(const char* fn, const mjs_actor_desc* desc, const mjs_actor_feature_inputs* blocks, mjs_actor** out) {
+  const std::string name = fn;
+  const bool visual = blocks != nullptr;
+  if (!desc || !out) return fail(nullptr, MJS_ERR_INVALID_ARG, name + ": null argument");
   *out = nullptr;
   if (desc->struct_size != sizeof(mjs_actor_desc))
-    return fail(nullptr, MJS_ERR_INVALID_ARG, "mjs_actor_create: mjs_actor_desc.struct_size does not match this library's header");
-  if (desc->in_dim < 1 || desc->in_dim > act::MAX_IN) return fail(nullptr, MJS_ERR_INVALID_ARG, "mjs_actor_create: in_dim must be 1..64");
-  if (desc->n_hidden < 1 || desc->n_hidden > act::MAX_LAYERS) return fail(nullptr, MJS_ERR_INVALID_ARG, "mjs_actor_create: n_hidden must be 1..3");
+    return fail(nullptr, MJS_ERR_INVALID_ARG, name + ": mjs_actor_desc.struct_size does not match this library's header");
+  if (desc->in_dim < (visual ? 0 : 1) || desc->in_dim > act::MAX_IN) return fail(nullptr, MJS_ERR_INVALID_ARG, name + (visual ? ": in_dim must be 0..64" : ": in_dim must be 1..64"));
+  if (desc->n_hidden < 1 || desc->n_hidden > act::MAX_LAYERS) return fail(nullptr, MJS_ERR_INVALID_ARG, name + ": n_hidden must be 1..3");
   for (int l = 0; l < desc->n_hidden; l++)
-    if (desc->hidden[l] < 1 || desc->hidden[l] > act::MAX_HIDDEN) return fail(nullptr, MJS_ERR_INVALID_ARG, "mjs_actor_create: every hidden width must be 1..256");
-  if (desc->action_dim < 1 || desc->action_dim > act::MAX_ACT) return fail(nullptr, MJS_ERR_INVALID_ARG, "mjs_actor_create: action_dim must be 1..8");
-  if (desc->activation != MJS_ACTIVATION_RELU && desc->activation != MJS_ACTIVATION_TANH) return fail(nullptr, MJS_ERR_INVALID_ARG, "mjs_actor_create: bad activation");
-  if (desc->variant != MJS_ACTOR_VARIANT_DEFAULT && desc->variant != MJS_ACTOR_VARIANT_TILE32) return fail(nullptr, MJS_ERR_INVALID_ARG, "mjs_actor_create: bad variant");
-  if (!desc->obs_index) return fail(nullptr, MJS_ERR_INVALID_ARG, "mjs_actor_create: obs_index is null");
+    if (desc->hidden[l] < 1 || desc->hidden[l] > act::MAX_HIDDEN) return fail(nullptr, MJS_ERR_INVALID_ARG, name + ": every hidden width must be 1..256");
+  if (desc->action_dim < 1 || desc->action_dim > act::MAX_ACT) return fail(nullptr, MJS_ERR_INVALID_ARG, name + ": action_dim must be 1..8");
+  if (desc->activation != MJS_ACTIVATION_RELU && desc->activation != MJS_ACTIVATION_TANH) return fail(nullptr, MJS_ERR_INVALID_ARG, name + ": bad activation");
+  if (desc->variant != MJS_ACTOR_VARIANT_DEFAULT && (visual || desc->variant != MJS_ACTOR_VARIANT_TILE32)) return fail(nullptr, MJS_ERR_INVALID_ARG, name + ": bad variant");
+  if (desc->in_dim > 0 && !desc->obs_index) return fail(nullptr, MJS_ERR_INVALID_ARG, name + ": obs_index is null");
   for (int j = 0; j < desc->in_dim; j++)
-    if (desc->obs_index[j] < 0) return fail(nullptr, MJS_ERR_INVALID_ARG, "mjs_actor_create: an obs_index entry is negative");
+    if (desc->obs_index[j] < 0) return fail(nullptr, MJS_ERR_INVALID_ARG, name + ": an obs_index entry is negative");
+  int in_total = desc->in_dim;
+  if (visual) {
+    if (blocks->struct_size != sizeof(mjs_actor_feature_inputs))
+      return fail(nullptr, MJS_ERR_INVALID_ARG, name + ": mjs_actor_feature_inputs.struct_size does not match this library's header");
+    int used = 0;
+    for (int b = 0; b < act::MAX_BLOCKS; b++) {
+      if (blocks->width[b] < 0 || blocks->width[b] > act::MAX_BLOCK_WIDTH) return fail(nullptr, MJS_ERR_INVALID_ARG, name + ": a block width must be 0 (absent) or 1..512");
+      used += blocks->width[b] > 0;
+      in_total += blocks->width[b];
+    }
+    if (used < 1 || used != blocks->n_blocks) return fail(nullptr, MJS_ERR_INVALID_ARG, name + ": n_blocks must be 1..2 and count the slots with a positive width");
+    for (int b = 0; b < act::MAX_BLOCKS; b++)
+      if (blocks->width[b] && (blocks->start[b] < 0 || blocks->start[b] + blocks->width[b] > in_total))
+        return fail(nullptr, MJS_ERR_INVALID_ARG, name + ": a block does not lie inside the input vector");
+    if (used == 2 && blocks->start[0] < blocks->start[1] + blocks->width[1] && blocks->start[1] < blocks->start[0] + blocks->width[0])
+      return fail(nullptr, MJS_ERR_INVALID_ARG, name + ": the blocks overlap");
+  }
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    return fail(nullptr, MJS_ERR_NO_DEVICE, "mjs_actor_create: no HIP device visible (this library has no CPU path)");
-  if (desc->device < 0 || desc->device >= ndev) return fail(nullptr, MJS_ERR_INVALID_ARG, "mjs_actor_create: device ordinal out of range");
+    return fail(nullptr, MJS_ERR_NO_DEVICE, name + ": no HIP device visible (this library has no CPU path)");
+  if (desc->device < 0 || desc->device >= ndev) return fail(nullptr, MJS_ERR_INVALID_ARG, name + ": device ordinal out of range");
   DeviceGuard dev_(desc->device);
   std::unique_ptr<mjs_actor, void (*)(mjs_actor*)> guard(new (std::nothrow) mjs_actor(), mjs_actor_destroy);
   mjs_actor* a = guard.get();
-  if (!a) return fail(nullptr, MJS_ERR_ALLOC, "mjs_actor_create: out of host memory");
-#define ACTOR_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return hip_fail(nullptr, e_, "mjs_actor_create: " #expr); } while (0)
+  if (!a) return fail(nullptr, MJS_ERR_ALLOC, name + ": out of host memory");
+#define ACTOR_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return hip_fail(nullptr, e_, (name + ": " #expr).c_str()); } while (0)
   ACTOR_TRY(dev_.err);
   a->desc = *desc;
-  a->index.assign(desc->obs_index, desc->obs_index + desc->in_dim);
-  a->desc.obs_index = a->index.data();
-  for (int32_t v : a->index) a->max_index = v > a->max_index ? v : a->max_index;
-  a->k0 = act::round_up(desc->in_dim, act::KPAD);
+  a->visual = visual;
+  a->in_total = in_total;
+  for (int j = 0; j < desc->in_dim; j++) a->max_index = desc->obs_index[j] > a->max_index ? desc->obs_index[j] : a->max_index;
+  if (!visual) {
+    a->index.assign(desc->obs_index, desc->obs_index + desc->in_dim);
+  } else {
+    // the input vector, position by position: a block's component (act::FeatureInputs' encoding) or the next observation column
+    a->index.assign((size_t)in_total, 0);
+    std::vector<bool> taken((size_t)in_total, false);
+    for (int b = 0; b < act::MAX_BLOCKS; b++) {
+      a->block_width[b] = blocks->width[b];
+      for (int f = 0; f < blocks->width[b]; f++) {
+        a->index[(size_t)(blocks->start[b] + f)] = -(1 + act::MAX_BLOCK_WIDTH * b + f);
+        taken[(size_t)(blocks->start[b] + f)] = true;
+      }
+    }
+    for (int j = 0, col = 0; j < in_total; j++)
+      if (!taken[(size_t)j]) a->index[(size_t)j] = desc->obs_index[col++];
+  }
+  a->desc.obs_index = visual ? nullptr : a->index.data();
+  a->k0 = act::round_up(in_total, act::KPAD);
   a->widest = a->k0 > act::OPAD ? a->k0 : act::OPAD;
   for (int l = 0; l < desc->n_hidden; l++) {
     a->width[l] = act::round_up(desc->hidden[l], act::OPAD);
@@ -792,13 +852,23 @@ int mjs_actor_create(const mjs_actor_desc* desc, mjs_actor** out) {
   }
   ACTOR_TRY(hipMalloc(&a->w[3], sizeof(float) * (size_t)K * act::OPAD));
   ACTOR_TRY(hipMalloc(&a->b[3], sizeof(float) * act::OPAD));
-  // the two LDS images of the 32-env kernel pass 64 KB from a widest layer of 256 on: an opt-in (gfx950 has 160 KB per CU)
-  static_assert(act::lds_bytes(32, act::MAX_HIDDEN) <= 160 * 1024 && act::lds_bytes(16, act::MAX_HIDDEN) <= 64 * 1024, "LDS images of the actor kernels");
+  // the two LDS images of the 32-env kernel pass 64 KB from a widest layer of 256 on: an opt-in (gfx950 has 160 KB per CU); so do
+  // those of the visual kernel from a first layer of 512 inputs on
+  constexpr int VISUAL_WIDEST = act::round_up(act::MAX_IN + act::MAX_BLOCKS * act::MAX_BLOCK_WIDTH, act::KPAD);
+  static_assert(act::lds_bytes(32, act::MAX_HIDDEN) <= 160 * 1024 && act::lds_bytes(16, act::MAX_HIDDEN) <= 64 * 1024 && act::lds_bytes(16, VISUAL_WIDEST) <= 160 * 1024,
+                "LDS images of the actor kernels");
   if (desc->variant == MJS_ACTOR_VARIANT_TILE32)
     ACTOR_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&act::kernel<32>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)act::lds_bytes(32, act::MAX_HIDDEN)));
+  if (visual)
+    ACTOR_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&act::kernel_visual), hipFuncAttributeMaxDynamicSharedMemorySize, (int)act::lds_bytes(16, VISUAL_WIDEST)));
 #undef ACTOR_TRY
   *out = guard.release();
   return MJS_OK;
+}
+int mjs_actor_create(const mjs_actor_desc* desc, mjs_actor** out) { return actor_create("mjs_actor_create", desc, nullptr, out); }
+int mjs_actor_create_visual(const mjs_actor_desc* desc, const mjs_actor_feature_inputs* blocks, mjs_actor** out) {
+  if (!blocks) return fail(nullptr, MJS_ERR_INVALID_ARG, "mjs_actor_create_visual: blocks is null");
+  return actor_create("mjs_actor_create_visual", desc, blocks, out);
 }
 
 void mjs_actor_destroy(mjs_actor* a) {
@@ -820,7 +890,7 @@ int mjs_actor_load(mjs_actor* a, const mjs_actor_weights* wts, void* stream) {
   if (!wts->mu_w || !wts->mu_b || !wts->log_std_w || !wts->log_std_b) return fail(nullptr, MJS_ERR_INVALID_ARG, "mjs_actor_load: a head's weight or bias is null");
   DeviceGuard dev_(a->desc.device);
   HIP_TRY(nullptr, dev_.err);
-  int in = a->desc.in_dim, K = a->k0;
+  int in = a->in_total, K = a->k0;
   for (int l = 0; l <= a->desc.n_hidden; l++) {
     const bool head = l == a->desc.n_hidden;
     act::PackParams p;
@@ -875,6 +945,179 @@ int mjs_rollout_actor(mjs_handle* h, const mjs_actor* actor, const double* obs0_
   return closed_loop(h, obs0_dev, T, loop, out, (hipStream_t)stream, [&](int32_t t, const double* obs, double* actions) {
     return launch_actor(h, actor, obs, roll->z_dev ? roll->z_dev + (size_t)t * NA : nullptr, roll->low, roll->high, actions,
                         roll->squashed_out_dev ? roll->squashed_out_dev + (size_t)t * NA : nullptr, (hipStream_t)stream);
+  });
+}
+
+// ---- visual policies: the NatureCNN encoder, feature blocks in the actor ----------------------------------------------------
+int mjs_encoder_create(const mjs_encoder_desc* desc, mjs_encoder** out) {
+  if (!desc || !out) return fail(nullptr, MJS_ERR_INVALID_ARG, "mjs_encoder_create: null argument");
+  *out = nullptr;
+  if (desc->struct_size != sizeof(mjs_encoder_desc))
+    return fail(nullptr, MJS_ERR_INVALID_ARG, "mjs_encoder_create: mjs_encoder_desc.struct_size does not match this library's header");
+  if (desc->height < enc::MIN_HW || desc->height > enc::MAX_HW || desc->width < enc::MIN_HW || desc->width > enc::MAX_HW)
+    return fail(nullptr, MJS_ERR_INVALID_ARG, "mjs_encoder_create: height and width must each be 36..96");
+  if (desc->channels != enc::C_IN) return fail(nullptr, MJS_ERR_INVALID_ARG, "mjs_encoder_create: channels must be 3");
+  if (desc->features_dim < 1 || desc->features_dim > enc::MAX_F) return fail(nullptr, MJS_ERR_INVALID_ARG, "mjs_encoder_create: features_dim must be 1..512");
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+    return fail(nullptr, MJS_ERR_NO_DEVICE, "mjs_encoder_create: no HIP device visible (this library has no CPU path)");
+  if (desc->device < 0 || desc->device >= ndev) return fail(nullptr, MJS_ERR_INVALID_ARG, "mjs_encoder_create: device ordinal out of range");
+  DeviceGuard dev_(desc->device);
+  std::unique_ptr<mjs_encoder, void (*)(mjs_encoder*)> guard(new (std::nothrow) mjs_encoder(), mjs_encoder_destroy);
+  mjs_encoder* e = guard.get();
+  if (!e) return fail(nullptr, MJS_ERR_ALLOC, "mjs_encoder_create: out of host memory");
+#define ENC_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return hip_fail(nullptr, e_, "mjs_encoder_create: " #expr); } while (0)
+  ENC_TRY(dev_.err);
+  e->desc = *desc;
+  e->g = enc::geometry(desc->height, desc->width);
+  e->Fp = enc::round_up(desc->features_dim, enc::FPAD);
+  const size_t wsize[4] = {(size_t)8 * 8 * enc::C_IN * enc::C1, (size_t)4 * 4 * enc::C1 * enc::C2, (size_t)3 * 3 * enc::C2 * enc::C3, (size_t)e->g.n_flatten * e->Fp};
+  const size_t bsize[4] = {(size_t)enc::C1, (size_t)enc::C2, (size_t)enc::C3, (size_t)e->Fp};
+  for (int l = 0; l < 4; l++) {
+    ENC_TRY(hipMalloc(&e->w[l], sizeof(float) * wsize[l]));
+    ENC_TRY(hipMalloc(&e->b[l], sizeof(float) * bsize[l]));
+  }
+  // one env's image and activations pass 64 KB of LDS from about 72x72 on: an opt-in (gfx950 has 160 KB per CU)
+  ENC_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&enc::conv_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)enc::lds_bytes(enc::geometry(enc::MAX_HW, enc::MAX_HW))));
+#undef ENC_TRY
+  *out = guard.release();
+  return MJS_OK;
+}
+
+void mjs_encoder_destroy(mjs_encoder* e) {
+  if (!e) return;
+  for (int l = 0; l < 4; l++) {
+    if (e->w[l]) (void)hipFree(e->w[l]);
+    if (e->b[l]) (void)hipFree(e->b[l]);
+  }
+  delete e;
+}
+
+int mjs_encoder_load(mjs_encoder* e, const mjs_encoder_weights* wts, void* stream) {
+  if (!e || !wts) return fail(nullptr, MJS_ERR_INVALID_ARG, "mjs_encoder_load: null argument");
+  if (wts->struct_size != sizeof(mjs_encoder_weights))
+    return fail(nullptr, MJS_ERR_INVALID_ARG, "mjs_encoder_load: mjs_encoder_weights.struct_size does not match this library's header");
+  if (!wts->conv1_w || !wts->conv1_b || !wts->conv2_w || !wts->conv2_b || !wts->conv3_w || !wts->conv3_b || !wts->fc_w || !wts->fc_b)
+    return fail(nullptr, MJS_ERR_INVALID_ARG, "mjs_encoder_load: a weight or bias is null");
+  DeviceGuard dev_(e->desc.device);
+  HIP_TRY(nullptr, dev_.err);
+  const enc::PackConvParams conv[3] = {{wts->conv1_w, wts->conv1_b, enc::C1, enc::C_IN, 8, 8, e->w[0], e->b[0]},
+                                       {wts->conv2_w, wts->conv2_b, enc::C2, enc::C1, 4, 4, e->w[1], e->b[1]},
+                                       {wts->conv3_w, wts->conv3_b, enc::C3, enc::C2, 3, 3, e->w[2], e->b[2]}};
+  for (const enc::PackConvParams& p : conv)
+    enc::pack_conv_kernel<<<dim3((unsigned)((p.kh * p.kw * p.cin * p.cout + 255) / 256)), 256, 0, (hipStream_t)stream>>>(p);
+  act::PackParams p;  // the linear layer: the actor's packing, one source
+  p.w0 = wts->fc_w; p.b0 = wts->fc_b; p.w1 = nullptr; p.b1 = nullptr;
+  p.out0 = e->desc.features_dim; p.out1 = 0;
+  p.in = e->g.n_flatten; p.K = e->g.n_flatten; p.O = e->Fp;
+  p.dst_w = e->w[3]; p.dst_b = e->b[3];
+  act::pack_kernel<<<dim3((unsigned)((p.K * p.O + 255) / 256)), 256, 0, (hipStream_t)stream>>>(p);
+  HIP_TRY(nullptr, hipGetLastError());
+  e->loaded = true;
+  return MJS_OK;
+}
+
+int mjs_encoder_flat_dim(const mjs_encoder* e) { return e ? e->g.n_flatten : -1; }
+uint64_t mjs_encoder_workspace_bytes(const mjs_encoder* e, int32_t n) { return e && n > 0 ? (uint64_t)n * (uint64_t)e->g.n_flatten * sizeof(float) : 0; }
+
+// the two launches of an encoder on the current device; arguments validated by the callers
+static int launch_encoder(mjs_handle* h, const mjs_encoder* e, const uint8_t* rgb, int n, void* workspace, float* features, hipStream_t s) {
+  enc::ConvParams c;
+  c.N = n; c.g = e->g; c.rgb = rgb;
+  c.W1 = e->w[0]; c.B1 = e->b[0]; c.W2 = e->w[1]; c.B2 = e->b[1]; c.W3 = e->w[2]; c.B3 = e->b[2];
+  c.flat = static_cast<float*>(workspace);
+  enc::conv_kernel<<<dim3((unsigned)n), enc::WAVES * 64, enc::lds_bytes(e->g), s>>>(c);
+  enc::FcParams f;
+  f.N = n; f.K = e->g.n_flatten; f.F = e->desc.features_dim; f.Fp = e->Fp;
+  f.flat = c.flat; f.W = e->w[3]; f.B = e->b[3]; f.out = features;
+  enc::fc_kernel<<<dim3((unsigned)((n + enc::FC_TE - 1) / enc::FC_TE)), enc::WAVES * 64, 0, s>>>(f);
+  HIP_TRY(h, hipGetLastError());
+  return MJS_OK;
+}
+
+int mjs_encoder_features(const mjs_encoder* e, const uint8_t* rgb_dev, int32_t n, void* workspace_dev, float* features_dev, void* stream) {
+  if (!e) return fail(nullptr, MJS_ERR_INVALID_ARG, "mjs_encoder_features: encoder is null");
+  if (n < 0) return fail(nullptr, MJS_ERR_INVALID_ARG, "mjs_encoder_features: n is negative");
+  if (!e->loaded) return fail(nullptr, MJS_ERR_INVALID_ARG, "mjs_encoder_features: the encoder has no parameters yet (mjs_encoder_load)");
+  if (n == 0) return MJS_OK;
+  if (!rgb_dev || !workspace_dev || !features_dev) return fail(nullptr, MJS_ERR_INVALID_ARG, "mjs_encoder_features: rgb_dev, workspace_dev or features_dev is null");
+  DeviceGuard dev_(e->desc.device);
+  HIP_TRY(nullptr, dev_.err);
+  return launch_encoder(nullptr, e, rgb_dev, n, workspace_dev, features_dev, (hipStream_t)stream);
+}
+
+// what both visual entry points refuse about the feature buffers; empty = fine
+static std::string features_refusal(const mjs_actor* a, const float* const* features) {
+  if (!features) return "features_dev is null";
+  for (int b = 0; b < act::MAX_BLOCKS; b++)
+    if (a->block_width[b] && !features[b]) return "a feature buffer of a block the actor has is null";
+  return "";
+}
+
+int mjs_actor_actions_visual(mjs_handle* h, const mjs_actor* actor, const double* obs_dev, const float* const features_dev[2], const float* z_dev,
+                             const double* low, const double* high, double* actions_dev, float* squashed_out_dev, void* stream) {
+  const std::string name = "mjs_actor_actions_visual";
+  if (!h) return fail(nullptr, MJS_ERR_INVALID_ARG, name + ": null handle");
+  std::string why = actor_refusal(h, actor, low, high, true);
+  if (why.empty()) why = features_refusal(actor, features_dev);
+  if (!why.empty()) return fail(h, MJS_ERR_INVALID_ARG, name + ": " + why);
+  if (!obs_dev || !actions_dev) return fail(h, MJS_ERR_INVALID_ARG, name + ": obs_dev or actions_dev is null");
+  DeviceGuard dev_(h->cfg.device);
+  HIP_TRY(h, dev_.err);
+  return launch_actor(h, actor, obs_dev, z_dev, low, high, actions_dev, squashed_out_dev, (hipStream_t)stream, features_dev);
+}
+
+int mjs_rollout_visual_actor(mjs_handle* h, const mjs_actor* actor, mjs_encoder* const encs[2], const double* obs0_dev, int32_t T,
+                             const mjs_visual_rollout* roll, const mjs_outputs* out, void* stream) {
+  const std::string name = "mjs_rollout_visual_actor";
+  if (!h) return fail(nullptr, MJS_ERR_INVALID_ARG, name + ": null handle");
+  if (!roll) return fail(h, MJS_ERR_INVALID_ARG, name + ": roll is null");
+  if (roll->struct_size != sizeof(mjs_visual_rollout))
+    return fail(h, MJS_ERR_INVALID_ARG, name + ": mjs_visual_rollout.struct_size does not match this library's header");
+  std::string why = actor_refusal(h, actor, roll->low, roll->high, true);
+  if (why.empty()) why = features_refusal(actor, roll->features_dev);
+  if (!why.empty()) return fail(h, MJS_ERR_INVALID_ARG, name + ": " + why);
+  if (!encs) return fail(h, MJS_ERR_INVALID_ARG, name + ": enc is null");
+  int32_t H = 0, W = 0;
+  for (int b = 0; b < act::MAX_BLOCKS; b++) {
+    const mjs_encoder* e = encs[b];
+    if (!e && actor->block_width[b]) return fail(h, MJS_ERR_INVALID_ARG, name + ": the actor has a feature block without an encoder");
+    if (!e) continue;
+    if (b == 1 && h->cfg.task != MJS_TASK_BUTTON_PUSH) return fail(h, MJS_ERR_INVALID_ARG, name + ": a wrist encoder on a task without a wrist camera");
+    if (!actor->block_width[b]) return fail(h, MJS_ERR_INVALID_ARG, name + ": an encoder for a feature block the actor does not have");
+    if (e->desc.device != h->cfg.device) return fail(h, MJS_ERR_INVALID_ARG, name + ": an encoder lives on another device than the handle");
+    if (!e->loaded) return fail(h, MJS_ERR_INVALID_ARG, name + ": an encoder has no parameters yet (mjs_encoder_load)");
+    if (e->desc.features_dim != actor->block_width[b]) return fail(h, MJS_ERR_INVALID_ARG, name + ": an encoder's features_dim is not the actor's block width");
+    if (H && (H != e->desc.height || W != e->desc.width)) return fail(h, MJS_ERR_INVALID_ARG, name + ": the two encoders have different image sizes");
+    H = e->desc.height; W = e->desc.width;
+  }
+  // the closed loop itself renders nothing here: the frames are the policy's input, taken in its own launches below
+  const ClosedLoop loop{roll->actions_out_dev, nullptr, nullptr, 0, 0};
+  why = closed_loop_refusal(h, "roll", T, loop, out);
+  if (!why.empty()) return fail(h, MJS_ERR_INVALID_ARG, name + ": " + why);
+  if (roll->wrist_rgb_dev && h->cfg.task != MJS_TASK_BUTTON_PUSH) return fail(h, MJS_ERR_INVALID_ARG, name + ": a wrist image buffer on a task without a wrist camera");
+  if (!roll->workspace_dev) return fail(h, MJS_ERR_INVALID_ARG, name + ": roll->workspace_dev is null");
+  uint8_t* const block_frames[2] = {roll->scene_rgb_dev, roll->wrist_rgb_dev};
+  uint8_t* const scratch[2] = {roll->scene_scratch_dev, roll->wrist_scratch_dev};
+  for (int b = 0; b < act::MAX_BLOCKS; b++)
+    if (encs[b] && !block_frames[b] && !scratch[b]) return fail(h, MJS_ERR_INVALID_ARG, name + ": a camera the actor uses has neither a [T, ...] buffer nor a one-step scratch");
+  if (T == 0) return MJS_OK;
+  if (!obs0_dev) return fail(h, MJS_ERR_INVALID_ARG, name + ": obs0_dev is null");
+  DeviceGuard dev_(h->cfg.device);
+  HIP_TRY(h, dev_.err);
+  const size_t N = (size_t)h->cfg.num_envs, NA = N * (size_t)h->inst.act_dim, frame = N * (size_t)H * (size_t)W * 3;
+  const hipStream_t s = (hipStream_t)stream;
+  return closed_loop(h, obs0_dev, T, loop, out, s, [&](int32_t t, const double* obs, double* actions) {
+    for (int b = 0; b < act::MAX_BLOCKS; b++) {
+      if (!encs[b] && !block_frames[b]) continue;
+      uint8_t* rgb = block_frames[b] ? block_frames[b] + (size_t)t * frame : scratch[b];
+      int rc = mjs_render(h, b == 0 ? MJS_CAMERA_SCENE : MJS_CAMERA_WRIST, H, W, rgb, stream);
+      if (rc == MJS_OK && encs[b]) rc = launch_encoder(h, encs[b], rgb, (int)N, roll->workspace_dev, roll->features_dev[b], s);
+      if (rc != MJS_OK) return rc;
+    }
+    return launch_actor(h, actor, obs, roll->z_dev ? roll->z_dev + (size_t)t * NA : nullptr, roll->low, roll->high, actions,
+                        roll->squashed_out_dev ? roll->squashed_out_dev + (size_t)t * NA : nullptr, s, roll->features_dev);
   });
 }
 

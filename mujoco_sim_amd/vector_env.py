@@ -426,20 +426,76 @@ class HipVectorEnv:
             return z
         return torch.randn(*lead, self.num_envs, self.action_dim, dtype=torch.float32, device=self.device, generator=generator)
 
+    @property
+    def camera_keys(self) -> tuple:
+        """The cameras this handle can render, under visual_observation_layout's keys and in its order (a DeviceActor's encoders
+        are keyed by them)."""
+        return ("ur5e/Camera/rgb_image", "Camera/rgb_image") if self.spec.name == "robot_push_button" else ("Camera/rgb_image",)
+
+    _CAMERA_IDS = {"Camera/rgb_image": 0, "ur5e/Camera/rgb_image": 1}  # slot of a visual actor = MJS_CAMERA_*
+
+    def _visual_scratch(self, actor):
+        """One step's frames, feature blocks and the encoders' workspace for a visual actor: allocated once per (actor, N)."""
+        if not hasattr(self, "_visual_scratch_of"):
+            self._visual_scratch_of = {}
+        entry = self._visual_scratch_of.get(id(actor))
+        if entry is None or entry[0] is not actor:
+            N, dev = self.num_envs, self.device
+            encs = [e for e in actor.encoders if e is not None]
+            h, w = encs[0].height, encs[0].width
+            scratch = {"frames": [torch.zeros(N, h, w, 3, dtype=torch.uint8, device=dev) if e is not None else None for e in actor.encoders],
+                       "features": [torch.zeros(N, e.features_dim, dtype=torch.float32, device=dev) if e is not None else None for e in actor.encoders],
+                       "workspace": torch.empty(N * max(e.flat_dim for e in encs), dtype=torch.float32, device=dev)}
+            scratch["feature_ptrs"] = (C.c_void_p * 2)(*[t.data_ptr() if t is not None else None for t in scratch["features"]])
+            entry = self._visual_scratch_of[id(actor)] = (actor, scratch)
+        return entry[1]
+
+    def _visual_features(self, actor, features):
+        """The (C.c_void_p * 2) of feature blocks for mjs_actor_actions_visual: the caller's (a dict by camera key), or the actor's
+        encoders run on fresh renders of this handle's state."""
+        if features is not None:
+            ptrs, keep = [None, None], []
+            for key, slot in self._CAMERA_IDS.items():
+                if actor.encoders[slot] is None:
+                    continue
+                t = features[key]
+                want = (self.num_envs, actor.encoders[slot].features_dim)
+                if tuple(t.shape) != want or t.dtype != torch.float32 or t.device != self.device or not t.is_contiguous():
+                    raise ValueError(f"features[{key!r}] must be a contiguous float32 tensor of shape {want} on {self.device}")
+                ptrs[slot] = t.data_ptr()
+                keep.append(t)
+            return (C.c_void_p * 2)(*ptrs)
+        scratch = self._visual_scratch(actor)
+        for slot, e in enumerate(actor.encoders):
+            if e is not None:
+                self.render(e.height, e.width, out=scratch["frames"][slot], camera=slot)
+                nat.check(self._lib.mjs_encoder_features(e._e, scratch["frames"][slot].data_ptr(), self.num_envs, scratch["workspace"].data_ptr(),
+                                                         scratch["features"][slot].data_ptr(), self._stream()))
+        return scratch["feature_ptrs"]
+
     def actor_actions(self, actor, deterministic: bool = False, generator: torch.Generator | None = None, out: torch.Tensor | None = None,
-                      z: torch.Tensor | None = None):
+                      z: torch.Tensor | None = None, features: dict | None = None):
         """A :class:`~mujoco_sim_amd.policies.DeviceActor` (SAC's MLP actor) for every env, from ``flat_obs``, in ONE launch:
         ``(actions [N, A] float64, squashed [N, A] float32)``. ``squashed`` = tanh(mu + exp(log_std) * z) (or tanh(mu) with
         ``deterministic``) is what SB3 stores in a replay buffer; ``actions`` is its affine image in the action space
         (SB3's ``unscale_action``, in float64), ready for :meth:`step`. The standard-normal draws ``z`` come from
         ``torch.randn(N, A, dtype=float32, generator=generator)`` on the device, or are the caller's ``z`` (float32 [N, A]).
-        ``out``: the action buffer to write."""
+        ``out``: the action buffer to write. A visual actor (``DeviceActor`` with ``encoders``) first renders the cameras it uses at
+        its encoders' image size and runs the encoders (scratch allocated once per actor and handle), whatever this handle's
+        ``observation_type``; ``features={camera key: float32 [N, F]}`` gives the feature blocks directly instead."""
         if out is None:
             out = torch.empty(self.num_envs, self.action_dim, dtype=torch.float64, device=self.device)
         assert out.shape == (self.num_envs, self.action_dim) and out.dtype == torch.float64 and out.is_contiguous()
         squashed = torch.empty(self.num_envs, self.action_dim, dtype=torch.float32, device=self.device)
         z = self._actor_z(deterministic, generator, z)
         low, high = self._action_bounds()
+        if getattr(actor, "visual", False):
+            feats = self._visual_features(actor, features)
+            nat.check(self._lib.mjs_actor_actions_visual(self._h, actor._a, self._buf["obs"].data_ptr(), C.byref(feats), z.data_ptr() if z is not None else None,
+                                                         low, high, out.data_ptr(), squashed.data_ptr(), self._stream()), self._h)
+            return out, squashed
+        if features is not None:
+            raise ValueError("features are a visual actor's input")
         nat.check(self._lib.mjs_actor_actions(self._h, actor._a, self._buf["obs"].data_ptr(), z.data_ptr() if z is not None else None, low, high,
                                               out.data_ptr(), squashed.data_ptr(), self._stream()), self._h)
         return out, squashed
@@ -452,7 +508,8 @@ class HipVectorEnv:
         Returns :meth:`demonstration_rollout`'s dict with ``"squashed_actions"`` [T, N, A] float32 in place of ``"ik_ok"``;
         ``LeRobotDatasetRecorder.record_rollout`` takes it unchanged. Equal, bit for bit, to T x (``actor_actions``; ``step``)
         with the same draws (``z``: float32 [T, N, A], slice t for step t; default ``torch.randn(T, N, A, generator=generator)``).
-        Afterwards ``flat_obs`` holds the block's last observation, so that calls chain."""
+        Afterwards ``flat_obs`` holds the block's last observation, so that calls chain. With a visual actor every step is render ->
+        encoder(s) -> actor -> step (mjs_rollout_visual_actor), on any handle; its frames (``render=True``) have the encoders' size."""
         T = int(T)
         if T < 0:
             raise ValueError("T must not be negative")
@@ -463,13 +520,29 @@ class HipVectorEnv:
         squashed = torch.zeros(T, N, self.action_dim, dtype=torch.float32, device=dev)
         z = self._actor_z(deterministic, generator, z, lead=(T,))
         images = {}
+        visual = getattr(actor, "visual", False)
         if render:
             r = self.image_resolution
-            if self.use_wrist_camera:
-                images["ur5e/Camera/rgb_image"] = torch.zeros(T, N, r, r, 3, dtype=torch.uint8, device=dev)
-            images["Camera/rgb_image"] = torch.zeros(T, N, r, r, 3, dtype=torch.uint8, device=dev)
-        if T:  # (an empty block needs no launch, and empty tensors have no address to pass)
-            ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+            hw = (r, r)
+            if visual:  # the frames are the encoders' input: their size, not the handle's
+                hw = next((e.height, e.width) for e in actor.encoders if e is not None)
+            if self.use_wrist_camera or (visual and actor.encoders[1] is not None):
+                images["ur5e/Camera/rgb_image"] = torch.zeros(T, N, *hw, 3, dtype=torch.uint8, device=dev)
+            images["Camera/rgb_image"] = torch.zeros(T, N, *hw, 3, dtype=torch.uint8, device=dev)
+        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        if T and visual:
+            low, high = self._action_bounds()
+            scratch = self._visual_scratch(actor)
+            roll = nat.MjsVisualRollout(z_dev=ptr(z), low=low, high=high, actions_out_dev=actions.data_ptr(), squashed_out_dev=squashed.data_ptr(),
+                                        scene_rgb_dev=ptr(images.get("Camera/rgb_image")), wrist_rgb_dev=ptr(images.get("ur5e/Camera/rgb_image")),
+                                        scene_scratch_dev=ptr(scratch["frames"][0]), wrist_scratch_dev=ptr(scratch["frames"][1]),
+                                        features_dev=scratch["feature_ptrs"], workspace_dev=scratch["workspace"].data_ptr())
+            encs = (C.c_void_p * 2)(*[e._e if e is not None else None for e in actor.encoders])
+            out = self._make_outputs(buf)
+            nat.check(self._lib.mjs_rollout_visual_actor(self._h, actor._a, C.byref(encs), self._buf["obs"].data_ptr(), T, C.byref(roll), C.byref(out),
+                                                         self._stream()), self._h)
+            self._buf["obs"].copy_(buf["obs"][-1])
+        elif T:  # (an empty block needs no launch, and empty tensors have no address to pass)
             low, high = self._action_bounds()
             roll = nat.MjsActorRollout(height=self.image_resolution, width=self.image_resolution, z_dev=ptr(z), low=low, high=high,
                                        actions_out_dev=actions.data_ptr(), squashed_out_dev=squashed.data_ptr(),
