@@ -53,6 +53,25 @@ struct ActorParams {
 
 __device__ __forceinline__ float activate(float x, int activation) { return activation == ACT_RELU ? fmaxf(x, 0.0f) : tanhf(x); }
 
+// 16 k of a 16x16 tile pair (v_mfma_f32_16x16x4_f32), for lane (r, kh) of a wavefront: the k loops of layer<16>, enc::conv and
+// enc::fc_kernel. `a` = 4 consecutive k, 4 kh + 0..3 of the 16, of the lane's A row r; `w` = the lane's B column pair at the first of
+// them, rows O floats apart; acc0 / acc1 = the tiles of the pair's two columns. Instruction s multiplies the k set {4 kh + s : kh = 0..3}.
+struct BColumnPair { float2 k[4]; };  // (only ever indexed by constants: registers)
+__device__ __forceinline__ BColumnPair load_b_k16(const float* __restrict__ w, int O) {
+  return {{*reinterpret_cast<const float2*>(w), *reinterpret_cast<const float2*>(w + O), *reinterpret_cast<const float2*>(w + 2 * O),
+           *reinterpret_cast<const float2*>(w + 3 * O)}};
+}
+__device__ __forceinline__ void tile_pair_k16(const f32x4 a, const BColumnPair& b, f32x4& acc0, f32x4& acc1) {
+#pragma unroll
+  for (int s = 0; s < 4; s++) {
+    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[s], b.k[s].x, acc0, 0, 0, 0);
+    acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[s], b.k[s].y, acc1, 0, 0, 0);
+  }
+}
+__device__ __forceinline__ void tile_pair_k16(const f32x4 a, const float* __restrict__ w, int O, f32x4& acc0, f32x4& acc1) {
+  tile_pair_k16(a, load_b_k16(w, O), acc0, acc1);
+}
+
 // One layer for the calling wavefront: Y[env][o] = act(sum_k X[env][k] W[k][o] + b[o]) for the 32-wide output groups
 // wave, wave + WAVES, ... below `O`; K a multiple of KPAD, O of OPAD. ACTIVATE false: the head (raw sums).
 template <int TE, bool ACTIVATE>
@@ -66,21 +85,7 @@ __device__ __forceinline__ void layer(const float* X, float* Y, int S, const flo
       f32x4 acc0 = {b.x, b.x, b.x, b.x}, acc1 = {b.y, b.y, b.y, b.y};
       const float* xrow = X + r * S + 4 * kh;
       const float* wcol = W + (size_t)(4 * kh) * O + c;
-      for (int kb = 0; kb < K; kb += 16) {
-        const f32x4 a = *reinterpret_cast<const f32x4*>(xrow + kb);
-        const float* w = wcol + (size_t)kb * O;
-        const float2 b0 = *reinterpret_cast<const float2*>(w), b1 = *reinterpret_cast<const float2*>(w + O);
-        const float2 b2 = *reinterpret_cast<const float2*>(w + 2 * O), b3 = *reinterpret_cast<const float2*>(w + 3 * O);
-        // instruction s multiplies the k set {kb + 4 kh + s : kh = 0..3}
-        acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[0], b0.x, acc0, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[0], b0.y, acc1, 0, 0, 0);
-        acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[1], b1.x, acc0, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[1], b1.y, acc1, 0, 0, 0);
-        acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[2], b2.x, acc0, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[2], b2.y, acc1, 0, 0, 0);
-        acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[3], b3.x, acc0, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[3], b3.y, acc1, 0, 0, 0);
-      }
+      for (int kb = 0; kb < K; kb += 16) tile_pair_k16(*reinterpret_cast<const f32x4*>(xrow + kb), wcol + (size_t)kb * O, O, acc0, acc1);
       // D: column = lane & 15 (here: the lane's column pair), row (env) = 4 (lane >> 4) + register
 #pragma unroll
       for (int q = 0; q < 4; q++) {
@@ -116,9 +121,10 @@ __device__ __forceinline__ void layer(const float* X, float* Y, int S, const flo
   }
 }
 
-// grid = ceil(N / TE) workgroups of WAVES wavefronts; dynamic LDS = lds_bytes(TE, widest layer)
-template <int TE>
-__global__ __launch_bounds__(WAVES * 64) void kernel(ActorParams p) {
+// The whole forward pass of a workgroup's TE envs: the inputs into LDS, the layers, the head, the squash and the unscale. gather(env, j) is
+// input j of an env as float32; it is the one thing the kernels below differ in.
+template <int TE, class Gather>
+__device__ __forceinline__ void forward(const ActorParams& p, Gather gather) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int S = p.S;
   float* buf0 = lds;
@@ -126,11 +132,11 @@ __global__ __launch_bounds__(WAVES * 64) void kernel(ActorParams p) {
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int env0 = blockIdx.x * TE;
 
-  // x: the selected observation columns, float64 -> float32 (round to nearest); rows of envs past N and the k padding are zero
+  // x: the gathered inputs; rows of envs past N and the k padding are zero
   for (int e = tid; e < TE * p.k0; e += WAVES * 64) {
     const int r = e / p.k0, j = e - r * p.k0;
     float x = 0.0f;
-    if (env0 + r < p.N && j < p.in_dim) x = (float)p.obs[(size_t)(env0 + r) * p.obs_dim + p.obs_index[j]];
+    if (env0 + r < p.N && j < p.in_dim) x = gather(env0 + r, j);
     buf0[r * S + j] = x;
   }
   __syncthreads();
@@ -193,83 +199,21 @@ struct FeatureInputs {
   int width[MAX_BLOCKS];
 };
 
-// The visual actor: kernel<16> line for line, except for where x comes from (a kernel of its own, so that the state actor's
-// instantiations stay the instructions they are). in_dim and k0 count the feature blocks (k0 up to 64 + 2 * 512: the LDS images
-// can pass 64 KB, an opt-in). grid = ceil(N / 16).
+// The kernels: grid = ceil(N / TE) workgroups of WAVES wavefronts; dynamic LDS = lds_bytes(TE, widest layer). The state actor's input j is
+// an observation column, float64 -> float32 (round to nearest) ...
+template <int TE>
+__global__ __launch_bounds__(WAVES * 64) void kernel(ActorParams p) {
+  forward<TE>(p, [obs = p.obs, obs_dim = p.obs_dim, index = p.obs_index](int env, int j) { return (float)obs[(size_t)env * obs_dim + index[j]]; });
+}
+// ... the visual actor's an observation column or a feature component, TE = 16. in_dim and k0 count the feature blocks (k0 up to
+// 64 + 2 * 512: the LDS images can pass 64 KB, an opt-in).
 __global__ __launch_bounds__(WAVES * 64) void kernel_visual(ActorParams p, FeatureInputs fi) {
-  constexpr int TE = 16;
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  const int S = p.S;
-  float* buf0 = lds;
-  float* buf1 = lds + TE * S;
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int env0 = blockIdx.x * TE;
-
-  // x: observation columns (float64 -> float32, round to nearest) and feature components; rows of envs past N and the k padding are zero
-  for (int e = tid; e < TE * p.k0; e += WAVES * 64) {
-    const int r = e / p.k0, j = e - r * p.k0;
-    float x = 0.0f;
-    if (env0 + r < p.N && j < p.in_dim) {
-      const int c = p.obs_index[j];
-      if (c >= 0) {
-        x = (float)p.obs[(size_t)(env0 + r) * p.obs_dim + c];
-      } else {
-        const int t = -1 - c, slot = t / MAX_BLOCK_WIDTH, f = t - slot * MAX_BLOCK_WIDTH;
-        x = slot == 0 ? fi.feat[0][(size_t)(env0 + r) * fi.width[0] + f] : fi.feat[1][(size_t)(env0 + r) * fi.width[1] + f];
-      }
-    }
-    buf0[r * S + j] = x;
-  }
-  __syncthreads();
-
-  // hidden layers (the launch's layer count is uniform), then the stacked head: mu in columns 0..A-1, log_std in A..2A-1
-  layer<TE, true>(buf0, buf1, S, p.W0, p.B0, p.k0, p.w0, p.activation, wave, lane);
-  __syncthreads();
-  const float* h = buf1;
-  float* other = buf0;
-  int K = p.w0;
-  if (p.n_hidden > 1) {
-    layer<TE, true>(buf1, buf0, S, p.W1, p.B1, p.w0, p.w1, p.activation, wave, lane);
-    __syncthreads();
-    h = buf0; other = buf1; K = p.w1;
-    if (p.n_hidden > 2) {
-      layer<TE, true>(buf0, buf1, S, p.W2, p.B2, p.w1, p.w2, p.activation, wave, lane);
-      __syncthreads();
-      h = buf1; other = buf0; K = p.w2;
-    }
-  }
-  layer<TE, false>(h, other, S, p.WH, p.BH, K, OPAD, p.activation, wave, lane);
-  __syncthreads();
-
-  // one thread per (env, action component)
-  const int A = p.A;
-  if (tid < TE * A) {
-    const int r = tid / A, j = tid - r * A, i = env0 + r;
-    if (i < p.N) {
-      const float mu = other[r * S + j];
-      const float ls = fminf(fmaxf(other[r * S + A + j], LOG_STD_MIN), LOG_STD_MAX);
-      float u = mu;
-      if (p.z) u = mu + expf(ls) * p.z[(size_t)i * A + j];
-      const float a = tanhf(u);
-      if (p.squashed) p.squashed[(size_t)i * A + j] = a;
-      double lo = p.low[0], hi = p.high[0];  // (a select chain: no indexed copy of the argument arrays)
-#pragma unroll
-      for (int k = 1; k < MAX_ACT; k++) {
-        lo = j == k ? p.low[k] : lo;
-        hi = j == k ? p.high[k] : hi;
-      }
-      {
-        // SB3's unscale_action, low + (0.5 * (a + 1.0) * (high - low)), operation by operation in float64: no contraction, so that
-        // the result is the one numpy / torch give for the stored squashed action
-#pragma clang fp contract(off)
-        const double t = (double)a + 1.0;
-        const double half = 0.5 * t;
-        const double span = hi - lo;
-        const double scaled = half * span;
-        p.actions[(size_t)i * A + j] = lo + scaled;
-      }
-    }
-  }
+  forward<16>(p, [&](int env, int j) {
+    const int c = p.obs_index[j];
+    if (c >= 0) return (float)p.obs[(size_t)env * p.obs_dim + c];
+    const int t = -1 - c, slot = t / MAX_BLOCK_WIDTH, f = t - slot * MAX_BLOCK_WIDTH;
+    return slot == 0 ? fi.feat[0][(size_t)env * fi.width[0] + f] : fi.feat[1][(size_t)env * fi.width[1] + f];
+  });
 }
 
 // torch.nn.Linear parameters (weight [out, in] row-major, bias [out]) -> the packed copy: dst_w [K][O], dst_b [O], K >= in, O >= out0 +

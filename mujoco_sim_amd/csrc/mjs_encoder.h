@@ -35,9 +35,9 @@ constexpr int FPAD = 32;         // granularity of the packed fc copy in the out
 constexpr int FC_TE = 16, FC_KC = 256, FC_S = FC_KC + 4, FC_GROUPS = MAX_F / 32 / WAVES;
 
 using act::f32x4;
+using act::round_up;
 
 constexpr int conv_out(int n, int k, int s) { return (n - k) / s + 1; }
-constexpr int round_up(int x, int m) { return (x + m - 1) / m * m; }
 
 struct Geometry {
   int H, W;
@@ -105,9 +105,7 @@ __device__ __forceinline__ void conv(const uint8_t* img, const float* lut, int R
         const int tap = k4 / CIN, c0 = k4 - tap * CIN, ky = tap / KW, kx = tap - ky * KW;
         off = (ky * Win + kx) * XS + c0;
       }
-      const float* w = Wt + (size_t)k4 * COUT + c;
-      const float2 b0 = *reinterpret_cast<const float2*>(w), b1 = *reinterpret_cast<const float2*>(w + COUT);
-      const float2 b2 = *reinterpret_cast<const float2*>(w + 2 * COUT), b3 = *reinterpret_cast<const float2*>(w + 3 * COUT);
+      const act::BColumnPair b = act::load_b_k16(Wt + (size_t)k4 * COUT + c, COUT);  // read once for the RT tiles
 #pragma unroll
       for (int j = 0; j < RT; j++) {
         if (tile0 + j < ntiles) {  // (uniform over the wavefront)
@@ -118,14 +116,7 @@ __device__ __forceinline__ void conv(const uint8_t* img, const float* lut, int R
           } else {
             a = *reinterpret_cast<const f32x4*>(X + base[j] + off);
           }
-          acc[j][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[0], b0.x, acc[j][0], 0, 0, 0);
-          acc[j][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[0], b0.y, acc[j][1], 0, 0, 0);
-          acc[j][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[1], b1.x, acc[j][0], 0, 0, 0);
-          acc[j][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[1], b1.y, acc[j][1], 0, 0, 0);
-          acc[j][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[2], b2.x, acc[j][0], 0, 0, 0);
-          acc[j][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[2], b2.y, acc[j][1], 0, 0, 0);
-          acc[j][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[3], b3.x, acc[j][0], 0, 0, 0);
-          acc[j][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[3], b3.y, acc[j][1], 0, 0, 0);
+          act::tile_pair_k16(a, b, acc[j][0], acc[j][1]);
         }
       }
     }
@@ -215,19 +206,8 @@ __global__ __launch_bounds__(WAVES * 64) void fc_kernel(FcParams p) {
 #pragma unroll
       for (int j = 0; j < FC_GROUPS; j++) {
         const int g = wave + WAVES * j;
-        if (g < ngroups) {  // (uniform over the wavefront)
-          const float* w = p.W + (size_t)(k0 + kb + 4 * kh) * p.Fp + g * 32 + 2 * r;
-          const float2 b0 = *reinterpret_cast<const float2*>(w), b1 = *reinterpret_cast<const float2*>(w + p.Fp);
-          const float2 b2 = *reinterpret_cast<const float2*>(w + 2 * p.Fp), b3 = *reinterpret_cast<const float2*>(w + 3 * p.Fp);
-          acc[j][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[0], b0.x, acc[j][0], 0, 0, 0);
-          acc[j][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[0], b0.y, acc[j][1], 0, 0, 0);
-          acc[j][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[1], b1.x, acc[j][0], 0, 0, 0);
-          acc[j][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[1], b1.y, acc[j][1], 0, 0, 0);
-          acc[j][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[2], b2.x, acc[j][0], 0, 0, 0);
-          acc[j][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[2], b2.y, acc[j][1], 0, 0, 0);
-          acc[j][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[3], b3.x, acc[j][0], 0, 0, 0);
-          acc[j][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[3], b3.y, acc[j][1], 0, 0, 0);
-        }
+        if (g < ngroups)  // (uniform over the wavefront)
+          act::tile_pair_k16(a, p.W + (size_t)(k0 + kb + 4 * kh) * p.Fp + g * 32 + 2 * r, p.Fp, acc[j][0], acc[j][1]);
       }
     }
   }

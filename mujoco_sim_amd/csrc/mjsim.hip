@@ -5,6 +5,7 @@
 #include <cstring>
 #include <memory>
 #include <new>
+#include <optional>
 #include <string>
 #include <vector>
 
@@ -165,6 +166,26 @@ int hip_fail(mjs_handle* h, hipError_t e, const char* what) {
     hipError_t e_ = (expr);                                \
     if (e_ != hipSuccess) return hip_fail(h, e_, #expr);   \
   } while (0)
+
+// a failing HIP call of a create function `fn` (the scope guard there frees what the object holds so far); `what` replaces the call's text
+#define CREATE_TRY(fn, expr, ...)                                                                                       \
+  do {                                                                                                                  \
+    hipError_t e_ = (expr);                                                                                             \
+    const char* what_ = "" __VA_ARGS__;                                                                                 \
+    if (e_ != hipSuccess) return hip_fail(nullptr, e_, (std::string(fn) + ": " + (*what_ ? what_ : #expr)).c_str());    \
+  } while (0)
+// what the create functions refuse about a device ordinal; MJS_OK = fine
+int device_refusal(const std::string& name, int device) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(nullptr, MJS_ERR_NO_DEVICE, name + ": no HIP device visible (this library has no CPU path)");
+  if (device < 0 || device >= ndev) return fail(nullptr, MJS_ERR_INVALID_ARG, name + ": device ordinal out of range");
+  return MJS_OK;
+}
+// the device buffers of an object that is being destroyed
+void free_all(std::initializer_list<void*> buffers) {
+  for (void* p : buffers)
+    if (p) (void)hipFree(p);
+}
 
 // Select the handle's device for the duration of one ABI call and restore the caller's current device afterwards
 // (torch's notion of the current device must not change behind its back). Same device: one hipGetDevice, no switch.
@@ -526,8 +547,8 @@ int closed_loop(mjs_handle* h, const double* obs0, int32_t T, const ClosedLoop& 
 }
 
 
-// what mjs_actor_actions and mjs_rollout_actor refuse about the pair (handle, actor); empty = fine
-std::string actor_refusal(const mjs_handle* h, const mjs_actor* a, const double* low, const double* high, bool visual = false) {
+// what the actor entry points refuse about the pair (handle, actor), `visual` for the two that take feature blocks; empty = fine
+std::string actor_refusal(const mjs_handle* h, const mjs_actor* a, const double* low, const double* high, bool visual) {
   if (!a) return "actor is null";
   if (a->visual != visual)
     return visual ? "the actor has no feature blocks (mjs_actor_create): use mjs_actor_actions / mjs_rollout_actor"
@@ -539,9 +560,17 @@ std::string actor_refusal(const mjs_handle* h, const mjs_actor* a, const double*
   if (!low || !high) return "low or high is null";
   return "";
 }
-// one launch of the actor kernel for every env of the handle; arguments validated by the callers
-int launch_actor(mjs_handle* h, const mjs_actor* a, const double* obs, const float* z, const double* low, const double* high, double* actions, float* squashed,
-                 hipStream_t s, const float* const* features = nullptr) {
+// what the visual entry points refuse about the feature buffers; empty = fine
+std::string features_refusal(const mjs_actor* a, const float* const* features) {
+  if (!features) return "features_dev is null";
+  for (int b = 0; b < act::MAX_BLOCKS; b++)
+    if (a->block_width[b] && !features[b]) return "a feature buffer of a block the actor has is null";
+  return "";
+}
+// one launch of the actor kernel for every env of the handle (features: a visual actor's blocks, nullptr otherwise); arguments
+// validated by the callers
+int launch_actor(mjs_handle* h, const mjs_actor* a, const double* obs, const float* const* features, const float* z, const double* low, const double* high,
+                 double* actions, float* squashed, hipStream_t s) {
   act::ActorParams p;
   std::memset(&p, 0, sizeof p);
   p.N = h->cfg.num_envs;
@@ -574,6 +603,52 @@ int launch_actor(mjs_handle* h, const mjs_actor* a, const double* obs, const flo
   HIP_TRY(h, hipGetLastError());
   return MJS_OK;
 }
+// mjs_actor_actions and (visual: with the feature blocks) mjs_actor_actions_visual
+int actor_actions(const char* fn, bool visual, mjs_handle* h, const mjs_actor* actor, const double* obs, const float* const* features, const float* z,
+                  const double* low, const double* high, double* actions, float* squashed, void* stream) {
+  const std::string name = fn;
+  if (!h) return fail(nullptr, MJS_ERR_INVALID_ARG, name + ": null handle");
+  std::string why = actor_refusal(h, actor, low, high, visual);
+  if (why.empty() && visual) why = features_refusal(actor, features);
+  if (!why.empty()) return fail(h, MJS_ERR_INVALID_ARG, name + ": " + why);
+  if (!obs || !actions) return fail(h, MJS_ERR_INVALID_ARG, name + ": obs_dev or actions_dev is null");
+  DeviceGuard dev_(h->cfg.device);
+  HIP_TRY(h, dev_.err);
+  return launch_actor(h, actor, obs, features, z, low, high, actions, squashed, (hipStream_t)stream);
+}
+
+// the loop of each rollout struct
+ClosedLoop loop_of(const mjs_demo_rollout& r) { return {r.actions_out_dev, r.scene_rgb_dev, r.wrist_rgb_dev, r.height, r.width}; }
+ClosedLoop loop_of(const mjs_actor_rollout& r) { return {r.actions_out_dev, r.scene_rgb_dev, r.wrist_rgb_dev, r.height, r.width}; }
+// (renders nothing itself: the frames are the policy's input, taken in its own launches)
+ClosedLoop loop_of(const mjs_visual_rollout& r) { return {r.actions_out_dev, nullptr, nullptr, 0, 0}; }
+std::string no_refusal() { return ""; }
+// The prologue of the three closed-loop rollouts, in the order they report it: the null handle, the null struct and its struct_size
+// (`arg` and `type` name it in the texts), the entry's own refusals, the loop's, the entry's late ones (the visual entry reports its
+// buffers after the loop's arguments), T == 0, obs0_dev, the handle's device. own(code) and late() run once `roll` may be read and
+// return a text, empty = fine; own may replace the code, MJS_ERR_INVALID_ARG. True: run the loop, `dev` holds the device; false:
+// return rc.
+template <class Roll, class Own, class Late>
+bool rollout_prologue(mjs_handle* h, const std::string& name, const char* arg, const char* type, const Roll* roll, const double* obs0, int32_t T,
+                      const mjs_outputs* out, Own own, Late late, ClosedLoop& loop, std::optional<DeviceGuard>& dev, int& rc) {
+  const auto refuse = [&](mjs_handle* hh, int code, const std::string& why) { rc = fail(hh, code, name + ": " + why); return false; };
+  if (!h) return refuse(nullptr, MJS_ERR_INVALID_ARG, "null handle");
+  if (!roll) return refuse(h, MJS_ERR_INVALID_ARG, std::string(arg) + " is null");
+  if (roll->struct_size != sizeof(Roll)) return refuse(h, MJS_ERR_INVALID_ARG, std::string(type) + ".struct_size does not match this library's header");
+  int code = MJS_ERR_INVALID_ARG;
+  std::string why = own(code);
+  if (!why.empty()) return refuse(h, code, why);
+  loop = loop_of(*roll);
+  why = closed_loop_refusal(h, arg, T, loop, out);
+  if (why.empty()) why = late();
+  if (!why.empty()) return refuse(h, MJS_ERR_INVALID_ARG, why);
+  rc = MJS_OK;
+  if (T == 0) return false;
+  if (!obs0) return refuse(h, MJS_ERR_INVALID_ARG, "obs0_dev is null");
+  dev.emplace(h->cfg.device);
+  if (dev->err != hipSuccess) { rc = hip_fail(h, dev->err, "dev_.err"); return false; }
+  return true;
+}
 }  // namespace
 
 extern "C" {
@@ -601,10 +676,8 @@ int mjs_substeps(int task) { return task == MJS_TASK_POINTMASS_REACH ? MJS_PM_NS
 
 const char* mjs_last_error(const mjs_handle* h) { return h ? h->err.c_str() : g_err.c_str(); }
 
-// a failing step of mjs_create: the scope guard there frees what the handle holds so far
-#define CREATE_TRY(what, expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return hip_fail(nullptr, e_, "mjs_create: " what); } while (0)
 #define LDS_OPT_IN(what, kernel, bytes) \
-  CREATE_TRY(what, hipFuncSetAttribute(reinterpret_cast<const void*>(&kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(bytes)))
+  CREATE_TRY("mjs_create", hipFuncSetAttribute(reinterpret_cast<const void*>(&kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(bytes)), what)
 
 int mjs_create(const mjs_config* cfg, mjs_handle** out) {
   if (!cfg || !out) return fail(nullptr, MJS_ERR_INVALID_ARG, "mjs_create: null argument");
@@ -622,10 +695,7 @@ int mjs_create(const mjs_config* cfg, mjs_handle** out) {
   if (cfg->num_envs <= 0) return fail(nullptr, MJS_ERR_INVALID_ARG, "mjs_create: num_envs must be positive");
   if (cfg->autoreset < MJS_AUTORESET_NEXT_STEP || cfg->autoreset > MJS_AUTORESET_DISABLED)
     return fail(nullptr, MJS_ERR_INVALID_ARG, "mjs_create: bad autoreset mode");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    return fail(nullptr, MJS_ERR_NO_DEVICE, "mjs_create: no HIP device visible (this library has no CPU path)");
-  if (cfg->device < 0 || cfg->device >= ndev) return fail(nullptr, MJS_ERR_INVALID_ARG, "mjs_create: device ordinal out of range");
+  if (int rc = device_refusal("mjs_create", cfg->device)) return rc;
   DeviceGuard dev_(cfg->device);  // ahead of the handle's guard: a failed create frees the handle while its device is still selected
   std::unique_ptr<mjs_handle, void (*)(mjs_handle*)> guard(new (std::nothrow) mjs_handle(), mjs_destroy);  // every early return cleans up
   mjs_handle* h = guard.get();
@@ -639,7 +709,7 @@ int mjs_create(const mjs_config* cfg, mjs_handle** out) {
   default_scene_camera(cfg->task, h->cam);
   const Instance& in = h->inst;
   const size_t N = (size_t)cfg->num_envs;
-  CREATE_TRY("device allocation", dev_.err);
+  CREATE_TRY("mjs_create", dev_.err, "device allocation");
   if (const char* bad_knob = read_ab_knobs(h->inst)) return fail(nullptr, MJS_ERR_INVALID_ARG, bad_knob);
   // > 64 KB of dynamic LDS per workgroup is an opt-in (gfx950 has 160 KB per CU): Planar-Push's cooperative workspaces + hull tables,
   // 16 envs per workgroup of the articulated-gripper kernel at large batches
@@ -650,31 +720,31 @@ int mjs_create(const mjs_config* cfg, mjs_handle** out) {
   static_assert(16 * sizeof(bg::Env) <= 160 * 1024, "16 envs per workgroup fit the CU's LDS");
   if (in.kind == KIND_PUSH2) { LDS_OPT_IN("device allocation", pp::kernel<false>, pp::LDS_BYTES); LDS_OPT_IN("device allocation", pp::kernel<true>, pp::LDS_BYTES); }
   if (in.kind == KIND_PUSH5) { LDS_OPT_IN("device allocation", pp5::kernel<false>, pp5::LDS_BYTES); LDS_OPT_IN("device allocation", pp5::kernel<true>, pp5::LDS_BYTES); }
-  CREATE_TRY("device allocation", hipMalloc(&h->state, sizeof(double) * in.state_dim * N));
-  CREATE_TRY("device allocation", hipMalloc(&h->flags, N));
-  CREATE_TRY("device allocation", hipMalloc(&h->rng_mt, sizeof(uint32_t) * 624 * N));
-  CREATE_TRY("device allocation", hipMalloc(&h->rng_pos, sizeof(int32_t) * N));
-  CREATE_TRY("device allocation", hipMemset(h->state, 0, sizeof(double) * in.state_dim * N));
-  if (in.nprim) CREATE_TRY("device allocation", hipMalloc(&h->prims, sizeof(float) * rend::PRIM_FLOATS * in.nprim * N));  // no allocation in launch paths
-  if (cfg->task == MJS_TASK_BUTTON_PUSH) CREATE_TRY("device allocation", hipMalloc(&h->cams, sizeof(float) * 12 * N));
-  if (in.kind == KIND_BUTTON_ARTICULATED) CREATE_TRY("device allocation", hipMalloc(&h->ws14, sizeof(double) * (size_t)bg::WS_DOUBLES * N));  // 15 KB per env: every row of every env
+  CREATE_TRY("mjs_create", hipMalloc(&h->state, sizeof(double) * in.state_dim * N), "device allocation");
+  CREATE_TRY("mjs_create", hipMalloc(&h->flags, N), "device allocation");
+  CREATE_TRY("mjs_create", hipMalloc(&h->rng_mt, sizeof(uint32_t) * 624 * N), "device allocation");
+  CREATE_TRY("mjs_create", hipMalloc(&h->rng_pos, sizeof(int32_t) * N), "device allocation");
+  CREATE_TRY("mjs_create", hipMemset(h->state, 0, sizeof(double) * in.state_dim * N), "device allocation");
+  if (in.nprim) CREATE_TRY("mjs_create", hipMalloc(&h->prims, sizeof(float) * rend::PRIM_FLOATS * in.nprim * N), "device allocation");  // no allocation in launch paths
+  if (cfg->task == MJS_TASK_BUTTON_PUSH) CREATE_TRY("mjs_create", hipMalloc(&h->cams, sizeof(float) * 12 * N), "device allocation");
+  if (in.kind == KIND_BUTTON_ARTICULATED) CREATE_TRY("mjs_create", hipMalloc(&h->ws14, sizeof(double) * (size_t)bg::WS_DOUBLES * N), "device allocation");  // 15 KB per env: every row of every env
   if (in.kind != KIND_POINTMASS)  // 3.4 KB per env, touched only by lanes with an arm geom in the floor
-    CREATE_TRY("device allocation", hipMalloc(&h->ws, sizeof(double) * rr::WS_ROWS * N));
+    CREATE_TRY("mjs_create", hipMalloc(&h->ws, sizeof(double) * rr::WS_ROWS * N), "device allocation");
 #ifdef MJS_STAMPS
-  CREATE_TRY("device allocation", hipMalloc(&h->stamps, sizeof(unsigned long long) * 16 * N));  // one slot block per workgroup, at most N workgroups
-  CREATE_TRY("device allocation", hipMemset(h->stamps, 0, sizeof(unsigned long long) * 16 * N));
+  CREATE_TRY("mjs_create", hipMalloc(&h->stamps, sizeof(unsigned long long) * 16 * N), "device allocation");  // one slot block per workgroup, at most N workgroups
+  CREATE_TRY("mjs_create", hipMemset(h->stamps, 0, sizeof(unsigned long long) * 16 * N), "device allocation");
 #endif
   if (in.kind == KIND_BUTTON_ARTICULATED) {
     LDS_OPT_IN("LDS opt-in", bg::kernel<false>, 16 * sizeof(bg::Env));
     LDS_OPT_IN("LDS opt-in", bg::kernel<true>, 16 * sizeof(bg::Env));
     // the compiled 14-body model: a __device__ global of this device, the same constants for every handle
     static const bg::Model host_model = [] { bg::Model m; std::memset(&m, 0, sizeof m); bg::build_model(m); return m; }();
-    CREATE_TRY("model upload", hipMemcpyToSymbol(HIP_SYMBOL(bg::g_model), &host_model, sizeof host_model));
+    CREATE_TRY("mjs_create", hipMemcpyToSymbol(HIP_SYMBOL(bg::g_model), &host_model, sizeof host_model), "model upload");
   }
   init_kernel<<<grid_for((int)N), BLOCK>>>(h->state, h->flags, (int)N, cfg->task, host_pending_byte(h));
   if (in.prog_row >= 0) fill_row_kernel<<<grid_for((int)N), BLOCK>>>(h->state + (size_t)in.prog_row * N, (int)N, -1.0);  // no next episode prepared
   seed_kernel<<<grid_for((int)N), BLOCK>>>(DevRng{h->rng_mt, h->rng_pos, (int)N}, 0u, cfg->env_index_offset);
-  CREATE_TRY("init kernels", hipDeviceSynchronize());
+  CREATE_TRY("mjs_create", hipDeviceSynchronize(), "init kernels");
   *out = guard.release();
   return MJS_OK;
 }
@@ -684,9 +754,7 @@ void mjs_destroy(mjs_handle* h) {  // the one place that frees what a handle own
 #ifdef MJS_STAMPS
   if (h->stamps) mjs_stamps_report(h->stamps, h->cfg.num_envs, h->cfg.task);
 #endif
-  for (void* p : {(void*)h->state, (void*)h->flags, (void*)h->rng_mt, (void*)h->rng_pos, (void*)h->stamps, (void*)h->prims, (void*)h->bg_ray, (void*)h->bg_rgb,
-                  (void*)h->cams, (void*)h->ws, (void*)h->ws14})
-    if (p) (void)hipFree(p);
+  free_all({h->state, h->flags, h->rng_mt, h->rng_pos, h->stamps, h->prims, h->bg_ray, h->bg_rgb, h->cams, h->ws, h->ws14});
   delete h;
 }
 
@@ -747,20 +815,11 @@ int mjs_demonstration_actions(mjs_handle* h, const double* obs_dev, const double
 }
 
 int mjs_rollout_demonstration(mjs_handle* h, const double* obs0_dev, int32_t T, const mjs_demo_rollout* demo, const mjs_outputs* out, void* stream) {
-  const std::string name = "mjs_rollout_demonstration";
-  if (!h) return fail(nullptr, MJS_ERR_INVALID_ARG, name + ": null handle");
-  if (!demo) return fail(h, MJS_ERR_INVALID_ARG, name + ": demo is null");
-  if (demo->struct_size != sizeof(mjs_demo_rollout))
-    return fail(h, MJS_ERR_INVALID_ARG, name + ": mjs_demo_rollout.struct_size does not match this library's header");
-  int code;
-  if (const char* why = policy_refusal(h, demo->noise, code)) return fail(h, code, name + ": " + why);
-  const ClosedLoop loop{demo->actions_out_dev, demo->scene_rgb_dev, demo->wrist_rgb_dev, demo->height, demo->width};
-  const std::string why = closed_loop_refusal(h, "demo", T, loop, out);
-  if (!why.empty()) return fail(h, MJS_ERR_INVALID_ARG, name + ": " + why);
-  if (T == 0) return MJS_OK;
-  if (!obs0_dev) return fail(h, MJS_ERR_INVALID_ARG, name + ": obs0_dev is null");
-  DeviceGuard dev_(h->cfg.device);
-  HIP_TRY(h, dev_.err);
+  ClosedLoop loop;
+  std::optional<DeviceGuard> dev_;
+  int rc;
+  const auto own = [&](int& code) -> std::string { const char* why = policy_refusal(h, demo->noise, code); return why ? why : ""; };
+  if (!rollout_prologue(h, "mjs_rollout_demonstration", "demo", "mjs_demo_rollout", demo, obs0_dev, T, out, own, no_refusal, loop, dev_, rc)) return rc;
   const size_t N = (size_t)h->cfg.num_envs;
   const size_t k = h->cfg.task == MJS_TASK_POINTMASS_REACH ? 2 : 3;  // noise draws per env
   return closed_loop(h, obs0_dev, T, loop, out, (hipStream_t)stream, [&](int32_t t, const double* obs, double* actions) {
@@ -805,16 +864,12 @@ static int actor_create(const char* fn, const mjs_actor_desc* desc, const mjs_ac
     if (used == 2 && blocks->start[0] < blocks->start[1] + blocks->width[1] && blocks->start[1] < blocks->start[0] + blocks->width[0])
       return fail(nullptr, MJS_ERR_INVALID_ARG, name + ": the blocks overlap");
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    return fail(nullptr, MJS_ERR_NO_DEVICE, name + ": no HIP device visible (this library has no CPU path)");
-  if (desc->device < 0 || desc->device >= ndev) return fail(nullptr, MJS_ERR_INVALID_ARG, name + ": device ordinal out of range");
+  if (int rc = device_refusal(name, desc->device)) return rc;
   DeviceGuard dev_(desc->device);
   std::unique_ptr<mjs_actor, void (*)(mjs_actor*)> guard(new (std::nothrow) mjs_actor(), mjs_actor_destroy);
   mjs_actor* a = guard.get();
   if (!a) return fail(nullptr, MJS_ERR_ALLOC, name + ": out of host memory");
-#define ACTOR_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return hip_fail(nullptr, e_, (name + ": " #expr).c_str()); } while (0)
-  ACTOR_TRY(dev_.err);
+  CREATE_TRY(name, dev_.err);
   a->desc = *desc;
   a->visual = visual;
   a->in_total = in_total;
@@ -842,26 +897,25 @@ static int actor_create(const char* fn, const mjs_actor_desc* desc, const mjs_ac
     a->width[l] = act::round_up(desc->hidden[l], act::OPAD);
     a->widest = a->width[l] > a->widest ? a->width[l] : a->widest;
   }
-  ACTOR_TRY(hipMalloc(&a->index_dev, sizeof(int32_t) * a->index.size()));
-  ACTOR_TRY(hipMemcpy(a->index_dev, a->index.data(), sizeof(int32_t) * a->index.size(), hipMemcpyHostToDevice));
+  CREATE_TRY(name, hipMalloc(&a->index_dev, sizeof(int32_t) * a->index.size()));
+  CREATE_TRY(name, hipMemcpy(a->index_dev, a->index.data(), sizeof(int32_t) * a->index.size(), hipMemcpyHostToDevice));
   int K = a->k0;
   for (int l = 0; l < desc->n_hidden; l++) {
-    ACTOR_TRY(hipMalloc(&a->w[l], sizeof(float) * (size_t)K * a->width[l]));
-    ACTOR_TRY(hipMalloc(&a->b[l], sizeof(float) * a->width[l]));
+    CREATE_TRY(name, hipMalloc(&a->w[l], sizeof(float) * (size_t)K * a->width[l]));
+    CREATE_TRY(name, hipMalloc(&a->b[l], sizeof(float) * a->width[l]));
     K = a->width[l];
   }
-  ACTOR_TRY(hipMalloc(&a->w[3], sizeof(float) * (size_t)K * act::OPAD));
-  ACTOR_TRY(hipMalloc(&a->b[3], sizeof(float) * act::OPAD));
+  CREATE_TRY(name, hipMalloc(&a->w[3], sizeof(float) * (size_t)K * act::OPAD));
+  CREATE_TRY(name, hipMalloc(&a->b[3], sizeof(float) * act::OPAD));
   // the two LDS images of the 32-env kernel pass 64 KB from a widest layer of 256 on: an opt-in (gfx950 has 160 KB per CU); so do
   // those of the visual kernel from a first layer of 512 inputs on
   constexpr int VISUAL_WIDEST = act::round_up(act::MAX_IN + act::MAX_BLOCKS * act::MAX_BLOCK_WIDTH, act::KPAD);
   static_assert(act::lds_bytes(32, act::MAX_HIDDEN) <= 160 * 1024 && act::lds_bytes(16, act::MAX_HIDDEN) <= 64 * 1024 && act::lds_bytes(16, VISUAL_WIDEST) <= 160 * 1024,
                 "LDS images of the actor kernels");
   if (desc->variant == MJS_ACTOR_VARIANT_TILE32)
-    ACTOR_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&act::kernel<32>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)act::lds_bytes(32, act::MAX_HIDDEN)));
+    CREATE_TRY(name, hipFuncSetAttribute(reinterpret_cast<const void*>(&act::kernel<32>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)act::lds_bytes(32, act::MAX_HIDDEN)));
   if (visual)
-    ACTOR_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&act::kernel_visual), hipFuncAttributeMaxDynamicSharedMemorySize, (int)act::lds_bytes(16, VISUAL_WIDEST)));
-#undef ACTOR_TRY
+    CREATE_TRY(name, hipFuncSetAttribute(reinterpret_cast<const void*>(&act::kernel_visual), hipFuncAttributeMaxDynamicSharedMemorySize, (int)act::lds_bytes(16, VISUAL_WIDEST)));
   *out = guard.release();
   return MJS_OK;
 }
@@ -873,11 +927,7 @@ int mjs_actor_create_visual(const mjs_actor_desc* desc, const mjs_actor_feature_
 
 void mjs_actor_destroy(mjs_actor* a) {
   if (!a) return;
-  if (a->index_dev) (void)hipFree(a->index_dev);
-  for (int l = 0; l < 4; l++) {
-    if (a->w[l]) (void)hipFree(a->w[l]);
-    if (a->b[l]) (void)hipFree(a->b[l]);
-  }
+  free_all({a->index_dev, a->w[0], a->w[1], a->w[2], a->w[3], a->b[0], a->b[1], a->b[2], a->b[3]});
   delete a;
 }
 
@@ -915,35 +965,19 @@ int mjs_actor_load(mjs_actor* a, const mjs_actor_weights* wts, void* stream) {
 
 int mjs_actor_actions(mjs_handle* h, const mjs_actor* actor, const double* obs_dev, const float* z_dev, const double* low, const double* high,
                       double* actions_dev, float* squashed_out_dev, void* stream) {
-  const std::string name = "mjs_actor_actions";
-  if (!h) return fail(nullptr, MJS_ERR_INVALID_ARG, name + ": null handle");
-  const std::string why = actor_refusal(h, actor, low, high);
-  if (!why.empty()) return fail(h, MJS_ERR_INVALID_ARG, name + ": " + why);
-  if (!obs_dev || !actions_dev) return fail(h, MJS_ERR_INVALID_ARG, name + ": obs_dev or actions_dev is null");
-  DeviceGuard dev_(h->cfg.device);
-  HIP_TRY(h, dev_.err);
-  return launch_actor(h, actor, obs_dev, z_dev, low, high, actions_dev, squashed_out_dev, (hipStream_t)stream);
+  return actor_actions("mjs_actor_actions", false, h, actor, obs_dev, nullptr, z_dev, low, high, actions_dev, squashed_out_dev, stream);
 }
 
 int mjs_rollout_actor(mjs_handle* h, const mjs_actor* actor, const double* obs0_dev, int32_t T, const mjs_actor_rollout* roll, const mjs_outputs* out,
                       void* stream) {
-  const std::string name = "mjs_rollout_actor";
-  if (!h) return fail(nullptr, MJS_ERR_INVALID_ARG, name + ": null handle");
-  if (!roll) return fail(h, MJS_ERR_INVALID_ARG, name + ": roll is null");
-  if (roll->struct_size != sizeof(mjs_actor_rollout))
-    return fail(h, MJS_ERR_INVALID_ARG, name + ": mjs_actor_rollout.struct_size does not match this library's header");
-  std::string why = actor_refusal(h, actor, roll->low, roll->high);
-  if (!why.empty()) return fail(h, MJS_ERR_INVALID_ARG, name + ": " + why);
-  const ClosedLoop loop{roll->actions_out_dev, roll->scene_rgb_dev, roll->wrist_rgb_dev, roll->height, roll->width};
-  why = closed_loop_refusal(h, "roll", T, loop, out);
-  if (!why.empty()) return fail(h, MJS_ERR_INVALID_ARG, name + ": " + why);
-  if (T == 0) return MJS_OK;
-  if (!obs0_dev) return fail(h, MJS_ERR_INVALID_ARG, name + ": obs0_dev is null");
-  DeviceGuard dev_(h->cfg.device);
-  HIP_TRY(h, dev_.err);
+  ClosedLoop loop;
+  std::optional<DeviceGuard> dev_;
+  int rc;
+  const auto own = [&](int&) { return actor_refusal(h, actor, roll->low, roll->high, false); };
+  if (!rollout_prologue(h, "mjs_rollout_actor", "roll", "mjs_actor_rollout", roll, obs0_dev, T, out, own, no_refusal, loop, dev_, rc)) return rc;
   const size_t NA = (size_t)h->cfg.num_envs * (size_t)h->inst.act_dim;
   return closed_loop(h, obs0_dev, T, loop, out, (hipStream_t)stream, [&](int32_t t, const double* obs, double* actions) {
-    return launch_actor(h, actor, obs, roll->z_dev ? roll->z_dev + (size_t)t * NA : nullptr, roll->low, roll->high, actions,
+    return launch_actor(h, actor, obs, nullptr, roll->z_dev ? roll->z_dev + (size_t)t * NA : nullptr, roll->low, roll->high, actions,
                         roll->squashed_out_dev ? roll->squashed_out_dev + (size_t)t * NA : nullptr, (hipStream_t)stream);
   });
 }
@@ -958,39 +992,31 @@ int mjs_encoder_create(const mjs_encoder_desc* desc, mjs_encoder** out) {
     return fail(nullptr, MJS_ERR_INVALID_ARG, "mjs_encoder_create: height and width must each be 36..96");
   if (desc->channels != enc::C_IN) return fail(nullptr, MJS_ERR_INVALID_ARG, "mjs_encoder_create: channels must be 3");
   if (desc->features_dim < 1 || desc->features_dim > enc::MAX_F) return fail(nullptr, MJS_ERR_INVALID_ARG, "mjs_encoder_create: features_dim must be 1..512");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    return fail(nullptr, MJS_ERR_NO_DEVICE, "mjs_encoder_create: no HIP device visible (this library has no CPU path)");
-  if (desc->device < 0 || desc->device >= ndev) return fail(nullptr, MJS_ERR_INVALID_ARG, "mjs_encoder_create: device ordinal out of range");
+  if (int rc = device_refusal("mjs_encoder_create", desc->device)) return rc;
   DeviceGuard dev_(desc->device);
   std::unique_ptr<mjs_encoder, void (*)(mjs_encoder*)> guard(new (std::nothrow) mjs_encoder(), mjs_encoder_destroy);
   mjs_encoder* e = guard.get();
   if (!e) return fail(nullptr, MJS_ERR_ALLOC, "mjs_encoder_create: out of host memory");
-#define ENC_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return hip_fail(nullptr, e_, "mjs_encoder_create: " #expr); } while (0)
-  ENC_TRY(dev_.err);
+  CREATE_TRY("mjs_encoder_create", dev_.err);
   e->desc = *desc;
   e->g = enc::geometry(desc->height, desc->width);
-  e->Fp = enc::round_up(desc->features_dim, enc::FPAD);
+  e->Fp = act::round_up(desc->features_dim, enc::FPAD);
   const size_t wsize[4] = {(size_t)8 * 8 * enc::C_IN * enc::C1, (size_t)4 * 4 * enc::C1 * enc::C2, (size_t)3 * 3 * enc::C2 * enc::C3, (size_t)e->g.n_flatten * e->Fp};
   const size_t bsize[4] = {(size_t)enc::C1, (size_t)enc::C2, (size_t)enc::C3, (size_t)e->Fp};
   for (int l = 0; l < 4; l++) {
-    ENC_TRY(hipMalloc(&e->w[l], sizeof(float) * wsize[l]));
-    ENC_TRY(hipMalloc(&e->b[l], sizeof(float) * bsize[l]));
+    CREATE_TRY("mjs_encoder_create", hipMalloc(&e->w[l], sizeof(float) * wsize[l]));
+    CREATE_TRY("mjs_encoder_create", hipMalloc(&e->b[l], sizeof(float) * bsize[l]));
   }
   // one env's image and activations pass 64 KB of LDS from about 72x72 on: an opt-in (gfx950 has 160 KB per CU)
-  ENC_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&enc::conv_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+  CREATE_TRY("mjs_encoder_create", hipFuncSetAttribute(reinterpret_cast<const void*>(&enc::conv_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)enc::lds_bytes(enc::geometry(enc::MAX_HW, enc::MAX_HW))));
-#undef ENC_TRY
   *out = guard.release();
   return MJS_OK;
 }
 
 void mjs_encoder_destroy(mjs_encoder* e) {
   if (!e) return;
-  for (int l = 0; l < 4; l++) {
-    if (e->w[l]) (void)hipFree(e->w[l]);
-    if (e->b[l]) (void)hipFree(e->b[l]);
-  }
+  free_all({e->w[0], e->w[1], e->w[2], e->w[3], e->b[0], e->b[1], e->b[2], e->b[3]});
   delete e;
 }
 
@@ -1047,65 +1073,47 @@ int mjs_encoder_features(const mjs_encoder* e, const uint8_t* rgb_dev, int32_t n
   return launch_encoder(nullptr, e, rgb_dev, n, workspace_dev, features_dev, (hipStream_t)stream);
 }
 
-// what both visual entry points refuse about the feature buffers; empty = fine
-static std::string features_refusal(const mjs_actor* a, const float* const* features) {
-  if (!features) return "features_dev is null";
-  for (int b = 0; b < act::MAX_BLOCKS; b++)
-    if (a->block_width[b] && !features[b]) return "a feature buffer of a block the actor has is null";
-  return "";
-}
-
 int mjs_actor_actions_visual(mjs_handle* h, const mjs_actor* actor, const double* obs_dev, const float* const features_dev[2], const float* z_dev,
                              const double* low, const double* high, double* actions_dev, float* squashed_out_dev, void* stream) {
-  const std::string name = "mjs_actor_actions_visual";
-  if (!h) return fail(nullptr, MJS_ERR_INVALID_ARG, name + ": null handle");
-  std::string why = actor_refusal(h, actor, low, high, true);
-  if (why.empty()) why = features_refusal(actor, features_dev);
-  if (!why.empty()) return fail(h, MJS_ERR_INVALID_ARG, name + ": " + why);
-  if (!obs_dev || !actions_dev) return fail(h, MJS_ERR_INVALID_ARG, name + ": obs_dev or actions_dev is null");
-  DeviceGuard dev_(h->cfg.device);
-  HIP_TRY(h, dev_.err);
-  return launch_actor(h, actor, obs_dev, z_dev, low, high, actions_dev, squashed_out_dev, (hipStream_t)stream, features_dev);
+  return actor_actions("mjs_actor_actions_visual", true, h, actor, obs_dev, features_dev, z_dev, low, high, actions_dev, squashed_out_dev, stream);
 }
 
 int mjs_rollout_visual_actor(mjs_handle* h, const mjs_actor* actor, mjs_encoder* const encs[2], const double* obs0_dev, int32_t T,
                              const mjs_visual_rollout* roll, const mjs_outputs* out, void* stream) {
-  const std::string name = "mjs_rollout_visual_actor";
-  if (!h) return fail(nullptr, MJS_ERR_INVALID_ARG, name + ": null handle");
-  if (!roll) return fail(h, MJS_ERR_INVALID_ARG, name + ": roll is null");
-  if (roll->struct_size != sizeof(mjs_visual_rollout))
-    return fail(h, MJS_ERR_INVALID_ARG, name + ": mjs_visual_rollout.struct_size does not match this library's header");
-  std::string why = actor_refusal(h, actor, roll->low, roll->high, true);
-  if (why.empty()) why = features_refusal(actor, roll->features_dev);
-  if (!why.empty()) return fail(h, MJS_ERR_INVALID_ARG, name + ": " + why);
-  if (!encs) return fail(h, MJS_ERR_INVALID_ARG, name + ": enc is null");
+  ClosedLoop loop;
+  std::optional<DeviceGuard> dev_;
+  int rc;
   int32_t H = 0, W = 0;
-  for (int b = 0; b < act::MAX_BLOCKS; b++) {
-    const mjs_encoder* e = encs[b];
-    if (!e && actor->block_width[b]) return fail(h, MJS_ERR_INVALID_ARG, name + ": the actor has a feature block without an encoder");
-    if (!e) continue;
-    if (b == 1 && h->cfg.task != MJS_TASK_BUTTON_PUSH) return fail(h, MJS_ERR_INVALID_ARG, name + ": a wrist encoder on a task without a wrist camera");
-    if (!actor->block_width[b]) return fail(h, MJS_ERR_INVALID_ARG, name + ": an encoder for a feature block the actor does not have");
-    if (e->desc.device != h->cfg.device) return fail(h, MJS_ERR_INVALID_ARG, name + ": an encoder lives on another device than the handle");
-    if (!e->loaded) return fail(h, MJS_ERR_INVALID_ARG, name + ": an encoder has no parameters yet (mjs_encoder_load)");
-    if (e->desc.features_dim != actor->block_width[b]) return fail(h, MJS_ERR_INVALID_ARG, name + ": an encoder's features_dim is not the actor's block width");
-    if (H && (H != e->desc.height || W != e->desc.width)) return fail(h, MJS_ERR_INVALID_ARG, name + ": the two encoders have different image sizes");
-    H = e->desc.height; W = e->desc.width;
-  }
-  // the closed loop itself renders nothing here: the frames are the policy's input, taken in its own launches below
-  const ClosedLoop loop{roll->actions_out_dev, nullptr, nullptr, 0, 0};
-  why = closed_loop_refusal(h, "roll", T, loop, out);
-  if (!why.empty()) return fail(h, MJS_ERR_INVALID_ARG, name + ": " + why);
-  if (roll->wrist_rgb_dev && h->cfg.task != MJS_TASK_BUTTON_PUSH) return fail(h, MJS_ERR_INVALID_ARG, name + ": a wrist image buffer on a task without a wrist camera");
-  if (!roll->workspace_dev) return fail(h, MJS_ERR_INVALID_ARG, name + ": roll->workspace_dev is null");
+  const auto own = [&](int&) -> std::string {
+    std::string why = actor_refusal(h, actor, roll->low, roll->high, true);
+    if (why.empty()) why = features_refusal(actor, roll->features_dev);
+    if (!why.empty()) return why;
+    if (!encs) return "enc is null";
+    for (int b = 0; b < act::MAX_BLOCKS; b++) {
+      const mjs_encoder* e = encs[b];
+      if (!e && actor->block_width[b]) return "the actor has a feature block without an encoder";
+      if (!e) continue;
+      if (b == 1 && h->cfg.task != MJS_TASK_BUTTON_PUSH) return "a wrist encoder on a task without a wrist camera";
+      if (!actor->block_width[b]) return "an encoder for a feature block the actor does not have";
+      if (e->desc.device != h->cfg.device) return "an encoder lives on another device than the handle";
+      if (!e->loaded) return "an encoder has no parameters yet (mjs_encoder_load)";
+      if (e->desc.features_dim != actor->block_width[b]) return "an encoder's features_dim is not the actor's block width";
+      if (H && (H != e->desc.height || W != e->desc.width)) return "the two encoders have different image sizes";
+      H = e->desc.height; W = e->desc.width;
+    }
+    return "";
+  };
+  const auto late = [&]() -> std::string {
+    if (roll->wrist_rgb_dev && h->cfg.task != MJS_TASK_BUTTON_PUSH) return "a wrist image buffer on a task without a wrist camera";
+    if (!roll->workspace_dev) return "roll->workspace_dev is null";
+    for (int b = 0; b < act::MAX_BLOCKS; b++)
+      if (encs[b] && !(b == 0 ? roll->scene_rgb_dev : roll->wrist_rgb_dev) && !(b == 0 ? roll->scene_scratch_dev : roll->wrist_scratch_dev))
+        return "a camera the actor uses has neither a [T, ...] buffer nor a one-step scratch";
+    return "";
+  };
+  if (!rollout_prologue(h, "mjs_rollout_visual_actor", "roll", "mjs_visual_rollout", roll, obs0_dev, T, out, own, late, loop, dev_, rc)) return rc;
   uint8_t* const block_frames[2] = {roll->scene_rgb_dev, roll->wrist_rgb_dev};
   uint8_t* const scratch[2] = {roll->scene_scratch_dev, roll->wrist_scratch_dev};
-  for (int b = 0; b < act::MAX_BLOCKS; b++)
-    if (encs[b] && !block_frames[b] && !scratch[b]) return fail(h, MJS_ERR_INVALID_ARG, name + ": a camera the actor uses has neither a [T, ...] buffer nor a one-step scratch");
-  if (T == 0) return MJS_OK;
-  if (!obs0_dev) return fail(h, MJS_ERR_INVALID_ARG, name + ": obs0_dev is null");
-  DeviceGuard dev_(h->cfg.device);
-  HIP_TRY(h, dev_.err);
   const size_t N = (size_t)h->cfg.num_envs, NA = N * (size_t)h->inst.act_dim, frame = N * (size_t)H * (size_t)W * 3;
   const hipStream_t s = (hipStream_t)stream;
   return closed_loop(h, obs0_dev, T, loop, out, s, [&](int32_t t, const double* obs, double* actions) {
@@ -1116,8 +1124,8 @@ int mjs_rollout_visual_actor(mjs_handle* h, const mjs_actor* actor, mjs_encoder*
       if (rc == MJS_OK && encs[b]) rc = launch_encoder(h, encs[b], rgb, (int)N, roll->workspace_dev, roll->features_dev[b], s);
       if (rc != MJS_OK) return rc;
     }
-    return launch_actor(h, actor, obs, roll->z_dev ? roll->z_dev + (size_t)t * NA : nullptr, roll->low, roll->high, actions,
-                        roll->squashed_out_dev ? roll->squashed_out_dev + (size_t)t * NA : nullptr, s, roll->features_dev);
+    return launch_actor(h, actor, obs, roll->features_dev, roll->z_dev ? roll->z_dev + (size_t)t * NA : nullptr, roll->low, roll->high, actions,
+                        roll->squashed_out_dev ? roll->squashed_out_dev + (size_t)t * NA : nullptr, s);
   });
 }
 

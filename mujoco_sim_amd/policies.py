@@ -41,12 +41,41 @@ def _camera_keys(venv) -> tuple:
     return tuple(keys) if keys is not None else (SCENE_CAMERA_KEY,)
 
 
-class DeviceEncoder:
+def _check_parameters(name, m, layer, owner, device):
+    """A layer's bias is there, and its parameters are float32 on ``device``; ValueError with the layer's ``name`` otherwise."""
+    if m.bias is None:
+        raise ValueError(f"{name}: a {layer} without bias")
+    for t in (m.weight, m.bias):
+        if t.dtype != torch.float32:
+            raise ValueError(f"{name}: parameters are {t.dtype}; the device {owner} is float32 by contract (module.float())")
+        if t.device != device:
+            raise ValueError(f"{name}: parameters live on {t.device}, the env on {device}")
+
+
+class _NativeObject:
+    """An object of libmjsim.so behind a Python one: the handle's attribute, and the call that destroys it."""
+    _handle, _destroy = "", ""
+
+    def close(self):
+        if getattr(self, self._handle, None):
+            torch.cuda.synchronize(self.device)
+            getattr(self._lib, self._destroy)(getattr(self, self._handle))
+            setattr(self, self._handle, None)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+
+class DeviceEncoder(_NativeObject):
     """SB3's ``NatureCNN`` (three ``Conv2d`` + ReLU, ``Flatten``, ``Linear`` + ReLU) held by libmjsim.so for the device of ``venv`` and
     one image size (csrc/mjs_encoder.h): uint8 [n, H, W, 3] frames, as :meth:`HipVectorEnv.render` writes them, to float32 features
     [n, F]. float32 with float32 accumulation; the division by 255 and the NHWC -> CHW reading are part of the kernel.
 
     Like :class:`DeviceActor` it keeps references to the torch modules and :meth:`load` packs their CURRENT parameters."""
+    _handle, _destroy = "_e", "mjs_encoder_destroy"
 
     def __init__(self, venv, conv1, conv2, conv3, fc, height, width):
         self._e = None
@@ -108,15 +137,13 @@ class DeviceEncoder:
                 raise ValueError(f"{name}: padding {m.padding!r}, NatureCNN's is 0")
             if (int(m.in_channels), int(m.out_channels)) != (cin, cout):
                 raise ValueError(f"{name}: channels {m.in_channels} -> {m.out_channels}, expected {cin} -> {cout}")
-            if m.bias is None:
-                raise ValueError(f"{name}: a Conv2d without bias")
+            _check_parameters(name, m, "Conv2d", "encoder", self.device)
             if tuple(m.weight.shape) != (cout, cin, k, k) or tuple(m.bias.shape) != (cout,):
                 raise ValueError(f"{name}: weight {tuple(m.weight.shape)} (dilation, groups?), expected {(cout, cin, k, k)}")
         fc = self.fc
         if not _is_linear(fc):
             raise ValueError(f"fc: {type(fc).__name__} is not a Linear layer")
-        if fc.bias is None:
-            raise ValueError("fc: a Linear without bias")
+        _check_parameters("fc", fc, "Linear", "encoder", self.device)
         if int(fc.in_features) != self.flat_dim:
             raise ValueError(f"fc.in_features is {fc.in_features}; a {self.height}x{self.width} image flattens to {self.flat_dim}")
         F = int(fc.out_features)
@@ -124,12 +151,6 @@ class DeviceEncoder:
             raise ValueError(f"fc: features_dim {F} outside 1..{nat.ENCODER_MAX_FEATURES}")
         if tuple(fc.weight.shape) != (F, self.flat_dim) or tuple(fc.bias.shape) != (F,):
             raise ValueError(f"fc: weight {tuple(fc.weight.shape)} / bias {tuple(fc.bias.shape)}, expected {(F, self.flat_dim)} / {(F,)}")
-        for name, m in (("conv1", self.convs[0]), ("conv2", self.convs[1]), ("conv3", self.convs[2]), ("fc", fc)):
-            for t in (m.weight, m.bias):
-                if t.dtype != torch.float32:
-                    raise ValueError(f"{name}: parameters are {t.dtype}; the device encoder is float32 by contract (module.float())")
-                if t.device != self.device:
-                    raise ValueError(f"{name}: parameters live on {t.device}, the env on {self.device}")
 
     def load(self):
         """Pack the modules' current parameters into the library's copy (small kernels on the current stream, no synchronisation)."""
@@ -166,25 +187,14 @@ class DeviceEncoder:
             nat.check(self._lib.mjs_encoder_features(self._e, images.data_ptr(), n, self.workspace(n).data_ptr(), out.data_ptr(), C.c_void_p(stream)))
         return out
 
-    def close(self):
-        if getattr(self, "_e", None):
-            torch.cuda.synchronize(self.device)
-            self._lib.mjs_encoder_destroy(self._e)
-            self._e = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass
-
-
-class DeviceActor:
+class DeviceActor(_NativeObject):
     """An MLP actor (SAC's squashed Gaussian) held by libmjsim.so for the device of ``venv``.
 
     The object keeps references to the torch modules; :meth:`load` packs their CURRENT parameters (a training loop calls it after
     every policy update; it enqueues small kernels on the current stream and never synchronises). An actor belongs to a device and
     a shape, not to a handle: any ``HipVectorEnv`` of the same task settings on that device may use it."""
+    _handle, _destroy = "_a", "mjs_actor_destroy"
 
     def __init__(self, venv, hidden, mu, log_std, activation="relu", obs_keys=None, obs_index=None, variant=nat.ACTOR_VARIANT_DEFAULT,
                  encoders=None, input_order=None):
@@ -393,17 +403,11 @@ class DeviceActor:
         for name, m, width in layers:
             if not 1 <= width <= nat.ACTOR_MAX_HIDDEN:
                 raise ValueError(f"{name}: width {width} outside 1..{nat.ACTOR_MAX_HIDDEN}")
-            if m.bias is None:
-                raise ValueError(f"{name}: a Linear without bias")
+            _check_parameters(name, m, "Linear", "actor", self.device)
             if name in ("mu", "log_std"):
                 fan_in = self.widths[-1]
             if tuple(m.weight.shape) != (width, fan_in) or tuple(m.bias.shape) != (width,):
                 raise ValueError(f"{name}: weight {tuple(m.weight.shape)} / bias {tuple(m.bias.shape)}, expected {(width, fan_in)} / {(width,)}")
-            for t in (m.weight, m.bias):
-                if t.dtype != torch.float32:
-                    raise ValueError(f"{name}: parameters are {t.dtype}; the device actor is float32 by contract (module.float())")
-                if t.device != self.device:
-                    raise ValueError(f"{name}: parameters live on {t.device}, the env on {self.device}")
             fan_in = width
 
     # ------------------------------------------------------------------ use
@@ -425,15 +429,6 @@ class DeviceActor:
             e.load()
 
     def close(self):
-        if getattr(self, "_a", None):
-            torch.cuda.synchronize(self.device)
-            self._lib.mjs_actor_destroy(self._a)
-            self._a = None
+        super().close()
         for e in getattr(self, "_owned_encoders", ()):
             e.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass

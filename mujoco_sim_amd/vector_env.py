@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 from . import _native as nat
+from .policies import _CAMERA_SLOTS, SCENE_CAMERA_KEY, WRIST_CAMERA_KEY
 from .spaces import Box, Dict, batch_box
 
 # reward / observation type strings of the reference (point_reach.py:11-17, robot_reach.py:37-41)
@@ -91,6 +92,10 @@ _BUTTON_EEF_ACTION_BOUNDS = ((-0.2, -0.6, 0.02, 0.0), (0.2, -0.3, 0.3, 0.085))  
 
 def _as_uint8_ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
 
 
 _RAW_STREAM = getattr(torch._C, "_cuda_getCurrentRawStream", None)
@@ -296,6 +301,21 @@ class HipVectorEnv:
         return {"is_success": b["is_success"], "discount": b["discount"], "step_type": b["step_type"], "fault": b["fault"],
                 "ncon": b["ncon"], "terminal_observation": self._obs_dict(b["terminal_obs"])}
 
+    def _block(self, T, keep):
+        """The [T, N, ...] output block of a rollout: a zeroed tensor per field of ``keep``, None for the others."""
+        return {k: (torch.zeros((T,) + tuple(v.shape), dtype=v.dtype, device=self.device) if k in keep else None) for k, v in self._buf.items()}
+
+    def _image_block(self, T, hw, wrist):
+        """The [T, N, H, W, 3] frames of a closed-loop block under visual_observation_layout's keys, in its order."""
+        keys = (WRIST_CAMERA_KEY, SCENE_CAMERA_KEY) if wrist else (SCENE_CAMERA_KEY,)
+        return {k: torch.zeros(T, self.num_envs, *hw, 3, dtype=torch.uint8, device=self.device) for k in keys}
+
+    def _finish_block(self, buf, images, **extra):
+        """The result dict of a closed-loop block; ``flat_obs`` takes the block's last observation, so that calls chain."""
+        if buf["obs"].shape[0]:
+            self._buf["obs"].copy_(buf["obs"][-1])
+        return {**{k: v for k, v in buf.items() if v is not None}, **extra, **images}
+
     # ----------------------------------------------------------------------- API
     def seed(self, seed: int):
         """env i <- np.random.RandomState(seed + env_index_offset + i) (dmc2gym.py:126-131; reach_sac.py:84)."""
@@ -340,7 +360,7 @@ class HipVectorEnv:
         a = torch.as_tensor(actions, device=self.device).to(torch.float64).contiguous()
         T = a.shape[0]
         assert a.shape == (T, self.num_envs, self.action_dim)
-        buf = {k: (torch.zeros((T,) + tuple(v.shape), dtype=v.dtype, device=self.device) if k in keep else None) for k, v in self._buf.items()}
+        buf = self._block(T, keep)
         out = self._make_outputs(buf)
         nat.check(self._lib.mjs_rollout(self._h, C.c_void_p(a.data_ptr()), T, C.byref(out), self._stream()), self._h)
         return {k: v for k, v in buf.items() if v is not None}
@@ -381,30 +401,18 @@ class HipVectorEnv:
         T = int(T)
         if T < 0:
             raise ValueError("T must not be negative")
-        N, dev = self.num_envs, self.device
-        keep = tuple(keep) + ("obs",)  # step t's policy reads slice t-1
-        buf = {k: (torch.zeros((T,) + tuple(v.shape), dtype=v.dtype, device=dev) if k in keep else None) for k, v in self._buf.items()}
+        N, dev, r = self.num_envs, self.device, self.image_resolution
+        buf = self._block(T, tuple(keep) + ("obs",))  # step t's policy reads slice t-1
         actions = torch.zeros(T, N, self.action_dim, dtype=torch.float64, device=dev)
         ok = torch.ones(T, N, dtype=torch.uint8, device=dev)
         z = self._noise_z(noise, generator, lead=(T,))
-        images = {}
-        if render:
-            r = self.image_resolution
-            if self.use_wrist_camera:
-                images["ur5e/Camera/rgb_image"] = torch.zeros(T, N, r, r, 3, dtype=torch.uint8, device=dev)
-            images["Camera/rgb_image"] = torch.zeros(T, N, r, r, 3, dtype=torch.uint8, device=dev)
+        images = self._image_block(T, (r, r), self.use_wrist_camera) if render else {}
         if T:  # (an empty block needs no launch, and empty tensors have no address to pass)
-            ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
-            demo = nat.MjsDemoRollout(height=self.image_resolution, width=self.image_resolution, noise=float(noise), noise_z_dev=ptr(z),
-                                      actions_out_dev=actions.data_ptr(), ik_ok_dev=ok.data_ptr(),
-                                      scene_rgb_dev=ptr(images.get("Camera/rgb_image")), wrist_rgb_dev=ptr(images.get("ur5e/Camera/rgb_image")))
+            demo = nat.MjsDemoRollout(height=r, width=r, noise=float(noise), noise_z_dev=_ptr(z), actions_out_dev=actions.data_ptr(), ik_ok_dev=ok.data_ptr(),
+                                      scene_rgb_dev=_ptr(images.get(SCENE_CAMERA_KEY)), wrist_rgb_dev=_ptr(images.get(WRIST_CAMERA_KEY)))
             out = self._make_outputs(buf)
             nat.check(self._lib.mjs_rollout_demonstration(self._h, self._buf["obs"].data_ptr(), T, C.byref(demo), C.byref(out), self._stream()), self._h)
-            self._buf["obs"].copy_(buf["obs"][-1])
-        res = {k: v for k, v in buf.items() if v is not None}
-        res["actions"], res["ik_ok"] = actions, ok.bool()
-        res.update(images)
-        return res
+        return self._finish_block(buf, images, actions=actions, ik_ok=ok.bool())
 
     # ------------------------------------------------------------------ learned policies on the device (policies.DeviceActor)
     def _action_bounds(self):
@@ -430,9 +438,7 @@ class HipVectorEnv:
     def camera_keys(self) -> tuple:
         """The cameras this handle can render, under visual_observation_layout's keys and in its order (a DeviceActor's encoders
         are keyed by them)."""
-        return ("ur5e/Camera/rgb_image", "Camera/rgb_image") if self.spec.name == "robot_push_button" else ("Camera/rgb_image",)
-
-    _CAMERA_IDS = {"Camera/rgb_image": 0, "ur5e/Camera/rgb_image": 1}  # slot of a visual actor = MJS_CAMERA_*
+        return (WRIST_CAMERA_KEY, SCENE_CAMERA_KEY) if self.spec.name == "robot_push_button" else (SCENE_CAMERA_KEY,)
 
     def _visual_scratch(self, actor):
         """One step's frames, feature blocks and the encoders' workspace for a visual actor: allocated once per (actor, N)."""
@@ -454,8 +460,8 @@ class HipVectorEnv:
         """The (C.c_void_p * 2) of feature blocks for mjs_actor_actions_visual: the caller's (a dict by camera key), or the actor's
         encoders run on fresh renders of this handle's state."""
         if features is not None:
-            ptrs, keep = [None, None], []
-            for key, slot in self._CAMERA_IDS.items():
+            ptrs = [None, None]
+            for key, slot in _CAMERA_SLOTS.items():  # (a visual actor's slot = MJS_CAMERA_*)
                 if actor.encoders[slot] is None:
                     continue
                 t = features[key]
@@ -463,7 +469,6 @@ class HipVectorEnv:
                 if tuple(t.shape) != want or t.dtype != torch.float32 or t.device != self.device or not t.is_contiguous():
                     raise ValueError(f"features[{key!r}] must be a contiguous float32 tensor of shape {want} on {self.device}")
                 ptrs[slot] = t.data_ptr()
-                keep.append(t)
             return (C.c_void_p * 2)(*ptrs)
         scratch = self._visual_scratch(actor)
         for slot, e in enumerate(actor.encoders):
@@ -513,47 +518,33 @@ class HipVectorEnv:
         T = int(T)
         if T < 0:
             raise ValueError("T must not be negative")
-        N, dev = self.num_envs, self.device
-        keep = tuple(keep) + ("obs",)  # step t's actor reads slice t-1
-        buf = {k: (torch.zeros((T,) + tuple(v.shape), dtype=v.dtype, device=dev) if k in keep else None) for k, v in self._buf.items()}
+        N, dev, r = self.num_envs, self.device, self.image_resolution
+        buf = self._block(T, tuple(keep) + ("obs",))  # step t's actor reads slice t-1
         actions = torch.zeros(T, N, self.action_dim, dtype=torch.float64, device=dev)
         squashed = torch.zeros(T, N, self.action_dim, dtype=torch.float32, device=dev)
         z = self._actor_z(deterministic, generator, z, lead=(T,))
-        images = {}
         visual = getattr(actor, "visual", False)
-        if render:
-            r = self.image_resolution
-            hw = (r, r)
-            if visual:  # the frames are the encoders' input: their size, not the handle's
-                hw = next((e.height, e.width) for e in actor.encoders if e is not None)
-            if self.use_wrist_camera or (visual and actor.encoders[1] is not None):
-                images["ur5e/Camera/rgb_image"] = torch.zeros(T, N, *hw, 3, dtype=torch.uint8, device=dev)
-            images["Camera/rgb_image"] = torch.zeros(T, N, *hw, 3, dtype=torch.uint8, device=dev)
-        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
-        if T and visual:
+        images = {}
+        if render and visual:  # the frames are the encoders' input: their size, not the handle's
+            images = self._image_block(T, next((e.height, e.width) for e in actor.encoders if e is not None), self.use_wrist_camera or actor.encoders[1] is not None)
+        elif render:
+            images = self._image_block(T, (r, r), self.use_wrist_camera)
+        if T:  # (an empty block needs no launch, and empty tensors have no address to pass)
             low, high = self._action_bounds()
-            scratch = self._visual_scratch(actor)
-            roll = nat.MjsVisualRollout(z_dev=ptr(z), low=low, high=high, actions_out_dev=actions.data_ptr(), squashed_out_dev=squashed.data_ptr(),
-                                        scene_rgb_dev=ptr(images.get("Camera/rgb_image")), wrist_rgb_dev=ptr(images.get("ur5e/Camera/rgb_image")),
-                                        scene_scratch_dev=ptr(scratch["frames"][0]), wrist_scratch_dev=ptr(scratch["frames"][1]),
-                                        features_dev=scratch["feature_ptrs"], workspace_dev=scratch["workspace"].data_ptr())
-            encs = (C.c_void_p * 2)(*[e._e if e is not None else None for e in actor.encoders])
+            shared = dict(z_dev=_ptr(z), low=low, high=high, actions_out_dev=actions.data_ptr(), squashed_out_dev=squashed.data_ptr(),
+                          scene_rgb_dev=_ptr(images.get(SCENE_CAMERA_KEY)), wrist_rgb_dev=_ptr(images.get(WRIST_CAMERA_KEY)))
             out = self._make_outputs(buf)
-            nat.check(self._lib.mjs_rollout_visual_actor(self._h, actor._a, C.byref(encs), self._buf["obs"].data_ptr(), T, C.byref(roll), C.byref(out),
-                                                         self._stream()), self._h)
-            self._buf["obs"].copy_(buf["obs"][-1])
-        elif T:  # (an empty block needs no launch, and empty tensors have no address to pass)
-            low, high = self._action_bounds()
-            roll = nat.MjsActorRollout(height=self.image_resolution, width=self.image_resolution, z_dev=ptr(z), low=low, high=high,
-                                       actions_out_dev=actions.data_ptr(), squashed_out_dev=squashed.data_ptr(),
-                                       scene_rgb_dev=ptr(images.get("Camera/rgb_image")), wrist_rgb_dev=ptr(images.get("ur5e/Camera/rgb_image")))
-            out = self._make_outputs(buf)
-            nat.check(self._lib.mjs_rollout_actor(self._h, actor._a, self._buf["obs"].data_ptr(), T, C.byref(roll), C.byref(out), self._stream()), self._h)
-            self._buf["obs"].copy_(buf["obs"][-1])
-        res = {k: v for k, v in buf.items() if v is not None}
-        res["actions"], res["squashed_actions"] = actions, squashed
-        res.update(images)
-        return res
+            if visual:
+                scratch = self._visual_scratch(actor)
+                roll = nat.MjsVisualRollout(scene_scratch_dev=_ptr(scratch["frames"][0]), wrist_scratch_dev=_ptr(scratch["frames"][1]),
+                                            features_dev=scratch["feature_ptrs"], workspace_dev=scratch["workspace"].data_ptr(), **shared)
+                encs = (C.c_void_p * 2)(*[e._e if e is not None else None for e in actor.encoders])
+                rc = self._lib.mjs_rollout_visual_actor(self._h, actor._a, C.byref(encs), self._buf["obs"].data_ptr(), T, C.byref(roll), C.byref(out), self._stream())
+            else:
+                roll = nat.MjsActorRollout(height=r, width=r, **shared)
+                rc = self._lib.mjs_rollout_actor(self._h, actor._a, self._buf["obs"].data_ptr(), T, C.byref(roll), C.byref(out), self._stream())
+            nat.check(rc, self._h)
+        return self._finish_block(buf, images, actions=actions, squashed_actions=squashed)
 
     @property
     def flat_observation_layout(self) -> tuple:
