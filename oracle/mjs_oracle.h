@@ -223,6 +223,19 @@ void om_render_pointmass(const om_env* e, int H, int W, uint8_t* out);
 void om_render_robot(const om_env* e, int H, int W, uint8_t* out);
 /* camera 0 = the task's scene camera, 1 = Button-Push wrist camera */
 void om_render_camera(const om_env* e, int camera, int H, int W, uint8_t* out);
+/* The three above are calls of this one with the task's default pose. camera 0: the scene camera at (pos[3], quat[4] (w, x, y, z;
+ * taken as given, normalised in float64), fovy degrees); NULL / NULL / <= 0 = the task's default. camera 1: the Button-Push wrist
+ * camera, which keeps its own view and lens but sees the scene camera's body at the pose. rgb uint8 [H, W, 3] and depth float32
+ * [H, W] (distance of the nearest hit along the optical axis, +inf where nothing is hit); either may be NULL. */
+void om_render_view(const om_env* e, int camera, const double* pos, const double* quat, double fovy, int H, int W, uint8_t* rgb, float* depth);
+/* robot scenes: the surface that wins each pixel, int32 [H, W]: -1 nothing, 0 the floor, k + 1 primitive k of om_scene_primitives */
+void om_render_winner(const om_env* e, int camera, const double* pos, const double* quat, double fovy, int H, int W, int32_t* winner);
+/* robot scenes: the render's float32 primitive records in test order: type (1 sphere, 2 capsule, 3 cylinder, 4 box), a[3], b[3],
+ * c[3], half[3], r, rgb[3]. sphere: a = centre; capsule / cylinder: a, b = the segment's ends; box: a = centre, b, c = two unit axes */
+#define OM_PRIM_FLOATS 17
+int om_scene_primitives(const om_env* e, const double* pos, const double* quat, float* out, int max);
+int om_max_prims(void);   /* the most records a scene has */
+int om_prim_floats(void); /* OM_PRIM_FLOATS, for the binding's layout check */
 void om_debug_button_dynamics(const double* q, const double* v, double* M_out, double* bias_out, double* invw_out);
 void om_debug_set_robot_state(om_env* e, const double* q, const double* v);
 void om_debug_link_invweights(int task, double* out7);

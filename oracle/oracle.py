@@ -17,6 +17,7 @@ STEP_FIRST, STEP_MID, STEP_LAST = 0, 1, 2
 REW_SPARSE, REW_DENSE_POTENTIAL, REW_DENSE_NEG_DISTANCE, REW_DENSE_BIASED_NEG_DISTANCE = 0, 1, 2, 3
 AUTORESET_NEXT_STEP, AUTORESET_SAME_STEP, AUTORESET_DISABLED = 0, 1, 2
 MAXOBS = 16
+MAX_PRIMS, PRIM_FLOATS = 32, 17  # OM_MAX_PRIMS (om_render.c), OM_PRIM_FLOATS (mjs_oracle.h): lib() checks both against the library
 
 
 class TaskConfig(C.Structure):
@@ -97,6 +98,12 @@ def lib() -> C.CDLL:
         L.om_render_pointmass.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         L.om_render_robot.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         L.om_render_camera.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        L.om_render_view.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.om_render_view.restype = None
+        L.om_render_winner.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_int, C.c_void_p]
+        L.om_render_winner.restype = None
+        L.om_scene_primitives.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        assert (L.om_max_prims(), L.om_prim_floats()) == (MAX_PRIMS, PRIM_FLOATS), "primitive record layout mismatch"
         L.om_rng_seed.argtypes = [C.POINTER(_Rng), C.c_uint32]
         L.om_rng_uniform.argtypes = [C.POINTER(_Rng), C.c_double, C.c_double]
         L.om_rng_uniform.restype = C.c_double
@@ -392,6 +399,48 @@ class OracleBatch:
         for i in range(self.n):
             lib().om_render_camera(lib().om_batch_env(self._h, i), camera, height, width, img[i].ctypes.data)
         return img
+
+    @staticmethod
+    def _pose_args(pose):
+        """(pos pointer, quat pointer, fovy, keep-alive) of a pose (position [3], quaternion [4] w x y z as given, fovy degrees);
+        None = the task's default."""
+        if pose is None:
+            return None, None, 0.0, None
+        pos = np.ascontiguousarray(pose[0], dtype=np.float64).reshape(3)
+        quat = np.ascontiguousarray(pose[1], dtype=np.float64).reshape(4)
+        return pos.ctypes.data, quat.ctypes.data, float(pose[2]), (pos, quat)
+
+    def render_rgbd(self, height: int, width: int, camera: int = 0, pose=None):
+        """(uint8 [N, H, W, 3], float32 [N, H, W]) of all envs with the scene camera at ``pose`` = (position, quaternion, fovy);
+        None = the task's default. Depth: the nearest hit's distance along the optical axis, +inf where nothing is hit. camera 1
+        (the Button-Push wrist camera) keeps its own view but sees the scene camera's body at the pose."""
+        L = lib()
+        pos, quat, fovy, _keep = self._pose_args(pose)
+        img = np.zeros((self.n, height, width, 3), dtype=np.uint8)
+        depth = np.zeros((self.n, height, width), dtype=np.float32)
+        for i in range(self.n):
+            L.om_render_view(L.om_batch_env(self._h, i), camera, pos, quat, fovy, height, width, img[i].ctypes.data, depth[i].ctypes.data)
+        return img, depth
+
+    def render_winner(self, height: int, width: int, camera: int = 0, pose=None) -> np.ndarray:
+        """robot scenes: which surface wins each pixel, int32 [N, H, W]: -1 nothing, 0 the floor, k + 1 row k of scene_primitives"""
+        L = lib()
+        pos, quat, fovy, _keep = self._pose_args(pose)
+        win = np.full((self.n, height, width), -1, dtype=np.int32)
+        for i in range(self.n):
+            L.om_render_winner(L.om_batch_env(self._h, i), camera, pos, quat, fovy, height, width, win[i].ctypes.data)
+        return win
+
+    def scene_primitives(self, pose=None) -> np.ndarray:
+        """robot scenes: the render's float32 primitive records in test order, [N, n, 17]: type (1 sphere, 2 capsule, 3 cylinder,
+        4 box), a[3], b[3], c[3], half[3], r, rgb[3]. sphere: a = centre; capsule / cylinder: a, b = the segment's ends; box: a =
+        centre, b and c = two unit axes (the third is b x c)."""
+        L = lib()
+        pos, quat, _fovy, _keep = self._pose_args(pose)
+        out = np.zeros((self.n, MAX_PRIMS, PRIM_FLOATS), dtype=np.float32)
+        counts = {L.om_scene_primitives(L.om_batch_env(self._h, i), pos, quat, out[i].ctypes.data, MAX_PRIMS) for i in range(self.n)}
+        assert len(counts) == 1, counts  # one task configuration per batch: every env has the same list length
+        return out[:, :counts.pop()].copy()
 
     def close(self):
         if self._h:

@@ -1,7 +1,8 @@
 """Configurable scene camera and depth output of the ray caster, on the GPU (include/mjsim.h: mjs_set_scene_camera,
 mjs_get_scene_camera, mjs_render_rgbd). The default views are pinned byte for byte by the oracle image tests of
 test_gpu_parity.py; everything here is checked from geometry alone: symmetries of the pinhole model (a rolled camera, a
-wider lens) against those pinned views, and unprojection of the depth map in numpy float64.
+wider lens) against those pinned views, and unprojection of the depth map in numpy float64. Moved poses (translated, re-aimed,
+close to the arm) and the depth maps of both cameras are pinned pixel by pixel against the oracle in test_camera_oracle.py.
 
 Bars. Images of two poses that see the same rays agree only to float32 rounding of the rays, so they are held to the bar the
 robot-scene images have against the oracle: differing bytes below 2e-4 of all bytes, none off by more than 2. Depth: float32

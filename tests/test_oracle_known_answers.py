@@ -309,6 +309,215 @@ def test_oracle_render_robot_scene(oracle_mod):
     assert (img[H - 1, 0] > 30).all() and abs(int(img[H - 1, 0, 0]) - int(img[H - 1, 0, 2])) < 3  # grey floor
 
 
+# ------------------------------------------------------------------------- moved scene cameras and depth (om_render_view)
+# The oracle's pose argument and depth output judge the kernels in test_camera_oracle.py; here they are made believable first,
+# from closed forms in float64 numpy and from the oracle's own symmetries. Poses, states and bars: tests/_camera_poses.py.
+import _camera_poses as cp  # noqa: E402
+
+ALL_CAMERA_TASKS = tuple(cp.TASK_IDS)
+
+
+@pytest.fixture(scope="module")
+def camera_states(oracle_mod):
+    """task -> the oracle batch after the image tests' few steps; built once, never stepped again."""
+    made = {}
+
+    def get(task):
+        if task not in made:
+            made[task] = cp.make_oracle(oracle_mod, task)[0]
+        return made[task]
+
+    return get
+
+
+@pytest.mark.parametrize("task", ALL_CAMERA_TASKS)
+def test_render_view_default_pose_is_the_old_entry_points_image(camera_states, task):
+    """pose=None, and the task's default numbers passed explicitly, give om_render_camera's image byte for byte; and that image is
+    the one the oracle rendered BEFORE it had a pose argument (tests/golden/oracle_default_views.npz: the first four envs of these
+    states, from the parent commit's om_render.c). All four tasks, both Button-Push cameras, 64x64 and 30x22."""
+    ob = camera_states(task)
+    golden = np.load(GOLDEN / "oracle_default_views.npz")
+    for cam in ((0, 1) if task == "robot_push_button" else (0,)):
+        for h, w in ((64, 64), (30, 22)):
+            old = ob.render(h, w, cam)
+            was = golden[f"{task}/camera{cam}/{h}x{w}"]
+            assert np.array_equal(old[:4], was), (task, cam, h, w, int((old[:4] != was).sum()))
+            for pose in (None, cp.DEFAULTS[task]):
+                rgb, depth = ob.render_rgbd(h, w, cam, pose)
+                assert np.array_equal(rgb, old), (task, cam, h, w, pose, int((rgb != old).sum()))
+                assert depth.dtype == np.float32 and depth.shape == (cp.N, h, w) and not np.isnan(depth).any() and (depth > 0).all()
+                # +inf exactly where nothing was hit: such a pixel is the background's black
+                assert (rgb[np.isposinf(depth)] == 0).all()
+
+
+def test_render_view_flat_floor_under_a_camera_that_looks_straight_down(camera_states):
+    """TOP_DOWN_CAMERA_CONFIG over Planar-Push: the arm works within |x| <= 0.2 and blocks and target spawn within |x| <= 0.15
+    (test_top_down_preset_on_planar_push), so the two outer strips whose rays meet the floor at |x| > 0.5 show nothing but floor:
+    z-depth = the camera's height whatever the pixel, to 1e-6 relative (float32: t and the axis cosine round to 6e-8 each)."""
+    ob = camera_states("robot_planar_push")
+    pose = cp.robot_poses("robot_planar_push")["top_down"]
+    height = pose[0][2]
+    for h, w in ((64, 64), (24, 40)):  # the second wider than high: its strips are wider still
+        _, depth = ob.render_rgbd(h, w, 0, pose)
+        d, _ = cp.rays(pose, h, w)
+        x_on_floor = pose[0][0] - height / d[..., 2] * d[..., 0]
+        strips = np.broadcast_to(np.abs(x_on_floor) > 0.5, depth.shape)
+        assert strips.mean() > 0.15
+        err = np.abs(depth[strips].astype(np.float64) - height) / height
+        print("flat floor", h, w, "max relative error", float(err.max()))
+        assert err.max() <= 1e-6, (h, w, float(err.max()))
+        assert (np.abs(depth.astype(np.float64) - height) <= 1e-6 * height).mean() > 0.5  # and the floor is most of the image
+
+
+@pytest.mark.parametrize("name", ["default", "tilted"])
+def test_render_view_pointmass_centre_pixel_reads_the_ray_sphere_root(camera_states, name):
+    """The pixel onto which the sphere's centre c projects looks along ITS OWN ray d (through the pixel's centre, off the axis and
+    off c), so its depth is the ray-sphere root t = -b - sqrt(b^2 - (|oc|^2 - r^2)), b = oc . d, oc = eye - c, times the axis
+    cosine -(d . back); the translucent sphere is a surface. Bar: float32 rounds b^2 and |oc|^2 - r^2 (both about |oc|^2 <= 6.3)
+    to 4e-7 each, a handful of such roundings make 2e-6 in the discriminant, whose root sqrt(disc) >= 0.04 (the pixel holds the
+    centre: the ray passes it within half a pixel's diagonal, 0.02 m) turns that into 2e-6 / (2 * 0.04) = 2.5e-5 m. Moving to
+    the next pixel changes the depth by a millimetre or more."""
+    ob = camera_states("point_mass_reach")
+    pose = cp.DEFAULTS["point_mass_reach"] if name == "default" else cp.POINTMASS_POSES["tilted"]
+    radius = 0.05  # MJS_PM_RADIUS (entities/pointmass.py:52)
+    qpos, _, _ = ob.get_state()
+    centre = np.concatenate([qpos[:, :2], np.full((cp.N, 1), radius)], axis=1)
+    eye = np.asarray(pose[0], dtype=np.float64)
+    right, up, back = cp.frame(pose[1])
+    for h, w in ((64, 64), (48, 72)):
+        _, depth = ob.render_rgbd(h, w, 0, pose)
+        d, cos_axis = cp.rays(pose, h, w)
+        v = centre - eye
+        z = -(v @ back)
+        th = np.tan(np.radians(pose[2]) / 2)
+        col = np.floor(((v @ right) / z / (th * w / h) + 1) / 2 * w).astype(int)
+        row = np.floor((1 - (v @ up) / z / th) / 2 * h).astype(int)
+        assert (z > 0).all() and (col >= 0).all() and (col < w).all() and (row >= 0).all() and (row < h).all()
+        dd = d[row, col]
+        oc = eye - centre
+        b = (oc * dd).sum(axis=1)
+        disc = b * b - ((oc * oc).sum(axis=1) - radius * radius)
+        assert (disc > 0.04 ** 2).all()
+        want = (-b - np.sqrt(disc)) * cos_axis[row, col]
+        got = depth[np.arange(cp.N), row, col].astype(np.float64)
+        print("pointmass centre", name, h, w, "max |depth - root * cosine|", float(np.abs(got - want).max()))
+        assert np.abs(got - want).max() <= 2.5e-5, (name, h, w, got - want)
+        off = depth[np.arange(cp.N), row, np.clip(col + 1, 0, w - 1)].astype(np.float64)
+        assert np.median(np.abs(off - want)) > 40 * 2.5e-5  # the bar tells this pixel from its neighbour
+
+
+@pytest.mark.parametrize("task", ALL_CAMERA_TASKS)
+def test_render_view_of_the_sky_is_black_and_infinitely_far(camera_states, task):
+    ob = camera_states(task)
+    cams = (0, 1) if task == "robot_push_button" else (0,)
+    for h, w in ((64, 64), (30, 22)):
+        rgb, depth = ob.render_rgbd(h, w, 0, cp.poses(task)["sky"])
+        assert not rgb.any() and np.isposinf(depth).all(), (task, h, w)
+    for cam in cams[1:]:  # the wrist camera keeps its own view whatever the scene camera looks at
+        assert ob.render_rgbd(64, 64, cam, cp.poses(task)["sky"])[0].std() > 10
+
+
+@pytest.mark.parametrize("task", cp.ROBOT_TASKS)
+def test_render_view_rolled_half_a_turn_is_the_image_upside_down(camera_states, task):
+    """default (x) 180 degrees about the optical axis: right and up change sign, pixel (r, c) sees what (H-1-r, W-1-c) saw. Wrong
+    frame columns (a transposed R, right and up swapped, a sign) break this. Bars of test_camera_views.py: below 2e-4 differing
+    bytes, none off by more than 2, depth within 1e-4 m."""
+    ob = camera_states(task)
+    pos, quat, fov = cp.DEFAULTS[task]
+    rolled = (pos, cp.quat_mul(quat, [0.0, 0.0, 0.0, 1.0]), fov)
+    for h, w in ((64, 64), (40, 24)):
+        rgb0, depth0 = ob.render_rgbd(h, w)
+        rgb1, depth1 = ob.render_rgbd(h, w, 0, rolled)
+        share, level = cp.image_shares(rgb1, rgb0[:, ::-1, ::-1])
+        dmax, dinf, _ = cp.depth_shares(depth1, depth0[:, ::-1, ::-1])
+        print(task, h, w, "rolled: bytes differing", share, "max", level, "depth max |delta|", dmax, "inf mask", dinf)
+        assert share < 2e-4 and level <= 2 and dmax <= cp.DEPTH_TOL and dinf == 0, (task, h, w, share, level, dmax, dinf)
+        assert not np.array_equal(rgb1, rgb0)
+
+
+def _moved_poses():
+    return [(task, name) for task in ALL_CAMERA_TASKS for name in cp.poses(task) if name != "sky"]
+
+
+@pytest.mark.parametrize("task,name", _moved_poses())
+def test_each_moved_pose_sees_something_and_the_bar_tells_it_from_2mm_away(camera_states, task, name):
+    """Oracle alone. (a) The pose is no bland one: image std > 10, more than 5 % of the pixels hit something, and at least one is
+    nearer than the floor's plane along its ray (a body, not only floor). (b) The bars of test_camera_oracle.py discriminate: the
+    same pose 2 mm aside changes more than ten times the share of bytes that the scene's bar lets differ (Point-Mass, whose bar is
+    bit for bit: any byte at all), and moves the depth of a share of pixels by more than DEPTH_TOL."""
+    ob = camera_states(task)
+    pose = cp.poses(task)[name]
+    rgb, depth = ob.render_rgbd(64, 64, 0, pose)
+    finite = np.isfinite(depth)
+    d, cos_axis = cp.rays(pose, 64, 64)
+    with np.errstate(divide="ignore"):
+        floor = np.where(d[..., 2] < 0, -pose[0][2] / d[..., 2] * cos_axis, np.inf)
+    nearer = finite & (depth < floor[None] - 1e-3)
+    assert rgb.std() > 10 and finite.mean() > 0.05 and nearer.any(), (task, name, float(rgb.std()), float(finite.mean()), int(nearer.sum()))
+    rgb2, depth2 = ob.render_rgbd(64, 64, 0, cp.shifted(pose))
+    byte_share, _ = cp.image_shares(rgb, rgb2)
+    _, _, depth_share = cp.depth_shares(depth, depth2)
+    print(f"DISCRIMINATION {task} {name} 64x64: bytes that differ 2 mm aside {byte_share:.4f} (bar {cp.BYTE_BAR[task]:g}), "
+          f"pixels whose depth moves by more than {cp.DEPTH_TOL:g} m {depth_share:.4f}")
+    assert byte_share > 10 * cp.BYTE_BAR[task] and byte_share > 0, (task, name, byte_share)
+    assert depth_share > 0, (task, name, depth_share)  # the depth bar allows no such pixel at all
+
+
+def test_wrist_camera_sees_the_scene_cameras_body_at_the_in_wrist_view_pose(camera_states):
+    """Oracle alone. The wrist camera's image depends on the scene pose only through the scene camera's body, and from the default
+    pose and the other poses of the table no wrist camera sees that body: their wrist images are one and the same. Pose
+    'in_wrist_view' puts the body where the wrist cameras look: its box must win pixels in at least half of the envs (its lens, a
+    sphere whose radius is the box's two small half sizes, lies within the box and can win no pixel from anywhere: its count is
+    printed, not asserted), and the wrist image and depth map must differ from the default-pose ones by more than ten times the image bar
+    (depth: in share of pixels) - so a body left at the default pose, or turned along other axes, fails the GPU comparison."""
+    task = "robot_push_button"
+    ob = camera_states(task)
+    table = cp.robot_poses(task)
+    pose = table["in_wrist_view"]
+    box, lens = (k + 1 for k in cp.WRIST_BODY_PRIMS)
+    for h, w in ((64, 64), (30, 22)):
+        rgb0, depth0 = ob.render_rgbd(h, w, 1, None)
+        for name in ("moved", "close_in", "behind", "top_down"):  # the blind poses: documented, so that nobody counts on them
+            win = ob.render_winner(h, w, 1, table[name])
+            assert not np.isin(win, (box, lens)).any(), name
+        win = ob.render_winner(h, w, 1, pose)
+        envs_box, envs_lens = (win == box).any(axis=(1, 2)).sum(), (win == lens).any(axis=(1, 2)).sum()
+        rgb1, depth1 = ob.render_rgbd(h, w, 1, pose)
+        byte_share, _ = cp.image_shares(rgb1, rgb0)
+        _, _, depth_share = cp.depth_shares(depth1, depth0)
+        rgb2, depth2 = ob.render_rgbd(h, w, 1, cp.shifted(pose))
+        print(f"DISCRIMINATION {task} wrist/in_wrist_view {h}x{w}: envs that see the box {envs_box} the lens {envs_lens} of {cp.N}, pixels of the body "
+              f"{int(np.isin(win, (box, lens)).sum())}; against the default pose: bytes {byte_share:.4f} (bar {cp.BYTE_BAR[task]:g}) depth pixels {depth_share:.4f}; "
+              f"2 mm aside: bytes {cp.image_shares(rgb1, rgb2)[0]:.4f} depth pixels {cp.depth_shares(depth1, depth2)[2]:.4f}")
+        assert envs_box >= cp.N // 2, (h, w, envs_box, envs_lens)
+        assert byte_share > 10 * cp.BYTE_BAR[task] and depth_share > 10 * cp.BYTE_BAR[task], (h, w, byte_share, depth_share)
+
+
+@pytest.mark.parametrize("task", cp.ROBOT_TASKS)
+def test_close_in_pose_keeps_the_eye_outside_every_primitive(camera_states, task):
+    """The close-in eye sits inside the arm's reach: it must stay at least 2 cm outside every primitive of every env (a ray that
+    starts inside a surface has no image definition), the scene camera's own body, which contains the eye by construction, aside;
+    and some primitives must really lie behind or across the camera plane."""
+    ob = camera_states(task)
+    pose = cp.robot_poses(task)["close_in"]
+    eye32 = np.asarray(pose[0], dtype=np.float32)
+    _, _, back = cp.frame(pose[1])
+    prims = ob.scene_primitives(pose)
+    behind = across = 0
+    for i in range(cp.N):
+        others = [r for r in prims[i] if not np.array_equal(r[1:4], eye32)]
+        assert len(others) == len(prims[i]) - (2 if task == "robot_push_button" else 0)
+        assert cp.clearance(others, pose[0]) >= 0.02, (task, i, cp.clearance(others, pose[0]))
+        for r in others:
+            ends = [r[1:4], r[4:7]] if int(r[0]) in (2, 3) else [r[1:4]]
+            reach = float(r[13]) if int(r[0]) != 4 else float(np.linalg.norm(r[10:13]))
+            z = [-(np.asarray(p, dtype=np.float64) - pose[0]) @ back for p in ends]
+            behind += max(z) + reach < 0
+            across += min(z) - reach < 0 < max(z) + reach
+    print(task, "close-in: primitives wholly behind the camera plane", behind, "across it", across)
+    assert behind >= 5 and across >= 5
+
+
 # ------------------------------------------------------------------------------------ Button-Push
 def test_button_push_reset_draw_order(oracle_mod):
     """initialize_episode (robot_push_button.py:126-134): robot spawn xyz, then switch xyz, each three sequential
