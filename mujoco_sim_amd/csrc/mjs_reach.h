@@ -249,6 +249,50 @@ MJS_DEV int actuator_forces(const double* q, const double* v, const double* ctrl
   }
   return clamped;
 }
+// Only the bit mask of actuator_forces, for a wavefront that needs nothing else of it (role 0 of the two dynamics wavefronts,
+// whose system matrix depends on which servos are force-clamped). The set-point is the substep loop's lerp
+// q0 + (q1 - q0) * (t - t0) * inv_span with its loop-invariant parts hoisted by the caller (d = q1 - q0, tt = t - t0), then the
+// same ctrl clamp and the same expression for f as above, bit for bit. clampd(f, -F, F) lands on a bound exactly when
+// |f| < F is false: f on or beyond a bound, or NaN (fmax / fmin drop the NaN and return the bound). So one test per joint
+// replaces the clamp and its two compares, with the same outcome for every input.
+// ctrl_inside (the same for the whole wavefront, servo_span_inside_ctrlrange below) says that the ctrl clamp cannot change
+// any set-point of this control step; it is then skipped: clampd returns an in-range argument itself, bit for bit.
+MJS_DEV int actuator_clamp_mask(const double* q, const double* v, const double* q0, const double* d, double tt, double inv_span, bool ctrl_inside) {
+  int clamped = 0;
+  double ctrl[NJ];
+#pragma unroll
+  for (int j = 0; j < NJ; j++) ctrl[j] = q0[j] + d[j] * tt * inv_span;
+  if (!ctrl_inside) {
+#pragma unroll
+    for (int j = 0; j < NJ; j++) ctrl[j] = clampd(ctrl[j], MJS_UR_ACT_CTRLRANGE[j][0], MJS_UR_ACT_CTRLRANGE[j][1]);
+  }
+#pragma unroll
+  for (int j = 0; j < NJ; j++) {
+    double cj = ctrl[j];
+    double f = MJS_UR_ACT_KP[j] * cj + 0.0 + (-MJS_UR_ACT_KP[j]) * q[j] + (-MJS_UR_ACT_KD[j]) * v[j];
+    if (!(fabs(f) < MJS_UR_ACT_FRC[j])) clamped |= 1 << j;
+  }
+  return clamped;
+}
+// Whether every set-point of a control step lies inside the actuators' ctrl range, for every lane of the wavefront. The lerp
+// q0 + d * tt * inv_span with 0 <= tt <= span stays between q0 and q1 up to a few ulps (three roundings), so both ends 1e-9
+// inside the range are enough. A NaN compares false and keeps the clamp.
+MJS_DEV bool servo_span_inside_ctrlrange(const double* q0, const double* q1) {
+  bool inside = true;
+#pragma unroll
+  for (int j = 0; j < NJ; j++) {
+    const double lo = MJS_UR_ACT_CTRLRANGE[j][0] + 1e-9, hi = MJS_UR_ACT_CTRLRANGE[j][1] - 1e-9;
+    inside = inside && q0[j] > lo && q0[j] < hi && q1[j] > lo && q1[j] < hi;
+  }
+  return !__any(!inside);
+}
+// mj_checkAcc: NaN / inf / |qacc| > 1e10 all make the sum of squares fail this one test
+MJS_DEV bool qacc_is_bad(const double* qacc) {
+  double acc2 = 0;
+#pragma unroll
+  for (int j = 0; j < NJ; j++) acc2 = fma(qacc[j], qacc[j], acc2);
+  return !(acc2 <= 1e20);
+}
 
 // implicitfast system matrix A = M + armature - dt * d(actuator)/dv and its factorisation
 // A = U D U^T with U unit UPPER triangular, eliminating from the wrist end (joint 5) towards the
@@ -1421,11 +1465,53 @@ __device__ __noinline__ void solo_tail(KernelParams p, int i, int lane, SoloTail
     return;                                                                                                                   \
   } while (0)
 
+// mj_checkAcc of the role loop is role 1's alone; neither wavefront has it between barrier 2 and the next barrier 1, where
+// the two are balanced to a few issue slots. Inside the loop role 1 checks substep s - 1's qacc between the two barriers of
+// substep s, where it otherwise only waits for role 0's solve (the opaque register uses keep the arithmetic in that window).
+MJS_DEV bool qacc_is_bad_while_waiting(double* qacc) {
+#pragma unroll
+  for (int j = 0; j < NJ; j++) asm volatile("" : "+v"(qacc[j]));
+  double acc2 = 0;
+#pragma unroll
+  for (int j = 0; j < NJ; j++) acc2 = fma(qacc[j], qacc[j], acc2);
+  asm volatile("" : "+v"(acc2));
+  return !(acc2 <= 1e20);
+}
+// After the loop: role 1 checks the last substep's qacc and hands the verdict to role 0 (which needs it once, for the epilogue)
+// through one LDS word per lane and one barrier. Both dynamics wavefronts call this.
+MJS_DEV bool hand_over_bad(int* bad_x, int lane, int role, bool bad, const double* last_qacc) {
+  if (role == 1) {
+    bad = bad || qacc_is_bad(last_qacc);
+    bad_x[lane] = bad;
+  }
+  __syncthreads();
+  return role == 1 ? bad : (bad_x[lane] != 0);
+}
+// Diagnostic build only (-DMJS_STAMPS -DMJS_MASK_COUNTERS): how often the clamp mask moves, counted per wave-substep of kernel3's
+// loop and summed over every launch of the handle (stamp slots 13-15 and 7 of the workgroup): substeps | some lane's mask differs
+// from its mask one substep earlier | some lane's mask is non-zero | lanes whose mask differs. The counters cost role 0 about
+// 600 cycles per substep, so the phase stamps of such a build say nothing: take those from a build without MJS_MASK_COUNTERS.
+#if defined(MJS_STAMPS) && defined(MJS_MASK_COUNTERS)
+#define MJS_MASK_STATS(p, mask, before)                                                            \
+  do {                                                                                             \
+    const unsigned long long ch_ = __ballot((mask) != (before)), nz_ = __ballot((mask) != 0);      \
+    if ((p).stamps && threadIdx.x == 0) {                                                          \
+      unsigned long long* c_ = (p).stamps + (size_t)blockIdx.x * 16;                               \
+      c_[13] += 1; c_[14] += ch_ != 0; c_[15] += nz_ != 0; c_[7] += __popcll(ch_);                 \
+    }                                                                                              \
+    (before) = (mask);                                                                             \
+  } while (0)
+#else
+#define MJS_MASK_STATS(p, mask, before) do { } while (0)
+#endif
+
 // ROLES == 1: one wavefront steps 64 envs. ROLES == 2 (default for stepping): two wavefronts of
 // one workgroup, placed on different SIMDs of the CU, step the same 64 envs: role 0 builds M(q),
 // factorises the implicitfast matrix (U D U^T) and inverts U while role 1 evaluates the servo
 // set-point, actuator forces and bias forces; they exchange 6 doubles per lane through LDS twice
-// per substep (qfrc_smooth ->, <- qacc) and integrate redundantly. Measured alternatives (same
+// per substep (qfrc_smooth ->, <- qacc) and integrate redundantly. Of the actuators role 0 evaluates only the clamp mask
+// (actuator_clamp_mask); mj_checkAcc is role 1's, done while it waits for role 0's solve (profiles/reach_clamp_mask_ab.txt:
+// the two are balanced to a few issue slots, only work taken off both shows). Measured alternatives (same
 // session A/B, profiles/r01_c_ab_roles.txt): one barrier per substep with both roles applying the
 // inverse (+2.0 us), contact detection on role 1 (+1.1 us), single wavefront (+5.0 us). Only role 0 touches HBM outputs and the RNG. The per-SIMD FP64 issue
 // rate is what bounds this kernel, so splitting the substep across SIMDs is the lever at
@@ -1437,6 +1523,7 @@ __global__ __launch_bounds__(64 * ROLES) void kernel(KernelParams p) {
   const int i = blockIdx.x * 64 + lane;
   __shared__ double xch[1][ROLES == 2 ? 12 : 1][64];  // rows 0-5: qfrc_smooth (role 1 -> 0), 6-11: qacc (role 0 -> 1)
   __shared__ double obs_tile[IS_RESET ? 1 : OBS_DIM * 64];  // wave-private transpose buffer for coalesced obs stores
+  __shared__ int bad_x[ROLES == 2 ? 64 : 1];                // mj_checkAcc's verdict (role 1 -> 0), once per control step
   if (i >= p.N) return;
   uint8_t flags = p.flags[i];
   if (ROLES == 2) __syncthreads();  // both wavefronts have read flags[i] before role 0 may rewrite it (see kernel3)
@@ -1473,9 +1560,13 @@ __global__ __launch_bounds__(64 * ROLES) void kernel(KernelParams p) {
     if (role != 0) return;
     MJS_RR_SOLO_TAIL(0, true);
   } else if constexpr (ROLES == 2) {
+    double dq01[NJ];  // the set-point lerp's loop-invariant difference (role 0's actuator_clamp_mask)
+#pragma unroll
+    for (int j = 0; j < NJ; j++) dq01[j] = q1[j] - q0[j];
+    const bool ctrl_inside = servo_span_inside_ctrlrange(q0, q1);
+    double qacc[NJ] = {0, 0, 0, 0, 0, 0};  // lives across substeps on role 1: it checks a substep's qacc during the next one's wait
 #pragma unroll 1
     for (int s = 0; s < MJS_RR_NSUB; s++) {
-      double qacc[NJ];
       if (role == 1) {
         // role 1: servo set-point, actuator forces and bias forces -> qfrc_smooth
         double t = fmin(fmax(st.time, t0), t1);
@@ -1487,18 +1578,17 @@ __global__ __launch_bounds__(64 * ROLES) void kernel(KernelParams p) {
 #pragma unroll
         for (int j = 0; j < NJ; j++) xch[0][j][lane] = fact[j] - bias[j];  // qfrc_smooth = -bias + actuator
         __syncthreads();  // qfrc_smooth published
+        bad = qacc_is_bad_while_waiting(qacc) || bad;  // the previous substep's
         __syncthreads();  // qacc published
 #pragma unroll
         for (int j = 0; j < NJ; j++) qacc[j] = xch[0][6 + j][lane];
       } else {
         // role 0: joint-space inertia, implicitfast matrix, U D U^T and U^-1, all before the barrier
-        // (overlapping role 1); the clamp mask is recomputed here (cheap)
+        // (overlapping role 1); only the clamp mask of the actuators is recomputed here
         if (s == 10) MJS_STAMP(p, 8);
         double t = fmin(fmax(st.time, t0), t1);
-        double ctrl[NJ], fdummy[NJ], M[21], A[NJ][NJ], W[NJ][NJ], Dinv[NJ], rhs[NJ];
-#pragma unroll
-        for (int j = 0; j < NJ; j++) ctrl[j] = q0[j] + (q1[j] - q0[j]) * (t - t0) * inv_span;
-        int clamped = actuator_forces(st.q, st.v, ctrl, fdummy);
+        double M[21], A[NJ][NJ], W[NJ][NJ], Dinv[NJ], rhs[NJ];
+        int clamped = actuator_clamp_mask(st.q, st.v, q0, dq01, t - t0, inv_span, ctrl_inside);
         ur5e_M_gen(cs, sn, M);
 #pragma unroll
         for (int r = 0; r < NJ; r++) {
@@ -1525,18 +1615,16 @@ __global__ __launch_bounds__(64 * ROLES) void kernel(KernelParams p) {
         __syncthreads();  // qacc published
         if (s == 10) MJS_STAMP(p, 11);
       }
-      // mj_checkAcc: NaN / inf / |qacc| > 1e10 all make the sum of squares fail this one test
-      double acc2 = 0, dq2 = 0;
+      // integration on both wavefronts (same bits); mj_checkAcc is role 1's alone (above), handed over after the loop
+      double dq2 = 0;
 #pragma unroll
       for (int j = 0; j < NJ; j++) {
-        acc2 = fma(qacc[j], qacc[j], acc2);
         st.v[j] += MJS_RR_PHYSICS_DT * qacc[j];
         double dq = MJS_RR_PHYSICS_DT * st.v[j];
         st.q[j] += dq;
         dq2 = fma(dq, dq, dq2);
         rotate_small(cs[j], sn[j], dq);
       }
-      bad = bad || !(acc2 <= 1e20);
       if (!(dq2 <= 0.01)) {  // some |dq| may exceed 0.1 rad (runaway state): fall back to the exact functions
 #pragma unroll
         for (int j = 0; j < NJ; j++) sincos(st.q[j], &sn[j], &cs[j]);
@@ -1544,6 +1632,7 @@ __global__ __launch_bounds__(64 * ROLES) void kernel(KernelParams p) {
       st.time += MJS_RR_PHYSICS_DT;
       if (role == 0 && s == 10) MJS_STAMP(p, 12);
     }
+    bad = hand_over_bad(bad_x, lane, role, bad, qacc);
   }
   // epilogue on both wavefronts (they hold the same numbers): role 1 writes the 25 state rows the step changed while role 0
   // works out observables, reward, flags and outputs. Not with the same-step auto-reset: role 0 may then rewrite the state rows
@@ -1615,6 +1704,7 @@ __global__ __launch_bounds__(192) void kernel3(KernelParams p) {
   const int i = (resetter ? (int)blockIdx.x - groups : (int)blockIdx.x) * 64 + lane;
   __shared__ double xch[12][64];    // rows 0-5: qfrc_smooth (role 1 -> 0), 6-11: qacc (role 0 -> 1)
   __shared__ double ikx[7][64];     // q1[6], found
+  __shared__ int bad_x[64];         // mj_checkAcc's verdict (role 1 -> 0), once per control step
   __shared__ double obs_tile[OBS_DIM * 64];
   if (i >= p.N) return;
   // Every wavefront takes the same branch below from its OWN read of flags[i]; wave 0 rewrites flags[i] in the epilogue. The
@@ -1673,6 +1763,7 @@ __global__ __launch_bounds__(192) void kernel3(KernelParams p) {
     load_cs(p, i, S_CS, cs, sn);
 #pragma unroll
     for (int j = 0; j < NJ; j++) v_start[j] = st.v[j];
+    [[maybe_unused]] int mask_before = 0;  // MJS_MASK_STATS (diagnostic build)
     {
       // substep 0, whole on this wavefront (both of them, same bits): ctrl = q0 (joint_trajectory.py:41-47 at t = t0)
       double M[21], bias[NJ], A[NJ][NJ], rhs[NJ], Dinv[NJ], fact[NJ], ctrl[NJ];
@@ -1686,6 +1777,7 @@ __global__ __launch_bounds__(192) void kernel3(KernelParams p) {
         for (int j = 0; j <= r; j++) A[r][j] = M[r * (r + 1) / 2 + j];
       }
       const int clamped = actuator_forces(st.q, st.v, ctrl, fact);
+      mask_before = clamped;
 #pragma unroll
       for (int j = 0; j < NJ; j++) rhs[j] = fact[j] - bias[j];
       factor_system(A, clamped, Dinv);
@@ -1719,9 +1811,13 @@ __global__ __launch_bounds__(192) void kernel3(KernelParams p) {
       if (role != 0) return;
       MJS_RR_SOLO_TAIL(1, false);  // no warm start across the hand-over: the first robust substep has no rows (guard), later ones start from it
     } else {
+      double dq01[NJ];  // the set-point lerp's loop-invariant difference (role 0's actuator_clamp_mask)
+#pragma unroll
+      for (int j = 0; j < NJ; j++) dq01[j] = q1[j] - q0[j];
+      const bool ctrl_inside = servo_span_inside_ctrlrange(q0, q1);
+      double qacc[NJ] = {0, 0, 0, 0, 0, 0};  // lives across substeps on role 1: it checks a substep's qacc during the next one's wait
 #pragma unroll 1
       for (int s = 1; s < MJS_RR_NSUB; s++) {
-        double qacc[NJ];
         if (role == 1) {
           double t = fmin(fmax(st.time, t0), t1);
           double ctrl[NJ], bias[NJ], fact[NJ];
@@ -1732,16 +1828,16 @@ __global__ __launch_bounds__(192) void kernel3(KernelParams p) {
 #pragma unroll
           for (int j = 0; j < NJ; j++) xch[j][lane] = fact[j] - bias[j];  // qfrc_smooth = -bias + actuator
           __syncthreads();  // qfrc_smooth published
+          bad = qacc_is_bad_while_waiting(qacc) || bad;  // the previous substep's
           __syncthreads();  // qacc published
 #pragma unroll
           for (int j = 0; j < NJ; j++) qacc[j] = xch[6 + j][lane];
         } else {
           if (s == 10) MJS_STAMP(p, 8);
           double t = fmin(fmax(st.time, t0), t1);
-          double ctrl[NJ], fdummy[NJ], M[21], A[NJ][NJ], W[NJ][NJ], Dinv[NJ], rhs[NJ];
-#pragma unroll
-          for (int j = 0; j < NJ; j++) ctrl[j] = q0[j] + (q1[j] - q0[j]) * (t - t0) * inv_span;
-          int clamped = actuator_forces(st.q, st.v, ctrl, fdummy);
+          double M[21], A[NJ][NJ], W[NJ][NJ], Dinv[NJ], rhs[NJ];
+          int clamped = actuator_clamp_mask(st.q, st.v, q0, dq01, t - t0, inv_span, ctrl_inside);
+          MJS_MASK_STATS(p, clamped, mask_before);
 #ifndef MJS_RR_SPLIT_FACTOR
           // M(q) + armature + dt kd -> U D U^T -> U^-1 as ONE generated, list-scheduled block (tools/gen_ur5e_dynamics.py factor_inverse:
           // the pivot chain runs next to the tail of the CRBA by construction; profiles/r04_g_*)
@@ -1784,17 +1880,16 @@ __global__ __launch_bounds__(192) void kernel3(KernelParams p) {
           __syncthreads();  // qacc published
           if (s == 10) MJS_STAMP(p, 11);
         }
-        double acc2 = 0, dq2 = 0;
+        // integration on both wavefronts (same bits); mj_checkAcc is role 1's alone (above), handed over after the loop
+        double dq2 = 0;
 #pragma unroll
         for (int j = 0; j < NJ; j++) {
-          acc2 = fma(qacc[j], qacc[j], acc2);
           st.v[j] += MJS_RR_PHYSICS_DT * qacc[j];
           double dq = MJS_RR_PHYSICS_DT * st.v[j];
           st.q[j] += dq;
           dq2 = fma(dq, dq, dq2);
           rotate_small(cs[j], sn[j], dq);
         }
-        bad = bad || !(acc2 <= 1e20);
         if (!(dq2 <= 0.01)) {
 #pragma unroll
           for (int j = 0; j < NJ; j++) sincos(st.q[j], &sn[j], &cs[j]);
@@ -1802,6 +1897,7 @@ __global__ __launch_bounds__(192) void kernel3(KernelParams p) {
         st.time += MJS_RR_PHYSICS_DT;
         if (role == 0 && s == 10) MJS_STAMP(p, 12);
       }
+      bad = hand_over_bad(bad_x, lane, role, bad, qacc);
       // epilogue on both wavefronts (same numbers): role 1 writes the 25 state rows the step changed while role 0 works out
       // observables, reward, flags and outputs (not with the same-step auto-reset: role 0 may then rewrite those rows)
       if (role == 1) {

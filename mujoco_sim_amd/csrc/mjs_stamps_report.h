@@ -37,5 +37,12 @@ inline void mjs_stamps_report(const unsigned long long* stamps_dev, int num_envs
   for (int w = 0; w < W; w++) own += (double)(host[16 * w + 6] - host[16 * w + 0]) / W;
   std::fprintf(stderr, "[MJS_STAMPS] cycles: load+IK %.0f (of which wave 0's own load + sincos + substep 0: %.0f) | substeps %.0f | fk+obs %.0f | contacts %.0f | store %.0f\n", d[0], own, d[1], d[2], d[3], d[4]);
   std::fprintf(stderr, "[MJS_STAMPS] role-0 substep 10: CRBA+factor+invert %.0f | barrier %.0f | apply inverse+publish+barrier %.0f | integrate %.0f\n", e[0], e[1], e[2], e[3]);
+  if (task == MJS_TASK_ROBOT_REACH) {  // MJS_MASK_STATS (mjs_reach.h): counters summed over every launch of the handle
+    double n = 0, changed = 0, nonzero = 0, lanes = 0;
+    for (int w = 0; w < W; w++) { n += (double)host[16 * w + 13]; changed += (double)host[16 * w + 14]; nonzero += (double)host[16 * w + 15]; lanes += (double)host[16 * w + 7]; }
+    if (n > 0)
+      std::fprintf(stderr, "[MJS_STAMPS] clamp mask, %.0f wave-substeps of the role loop: some lane's mask differs from one substep earlier %.4f | some lane's mask non-zero %.4f | lane-substeps whose mask differs %.5f\n",
+                   n, changed / n, nonzero / n, lanes / (64 * n));
+  }
   delete[] host;
 }

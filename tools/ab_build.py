@@ -4,7 +4,8 @@ ab/libmjsim_<name>.so (git-ignored, travels with gpurun). Usage:
 Load with MJS_LIB=ab/libmjsim_NAME.so (bypasses the source-hash check: never for tests or published numbers).
   --flag=-DMJS_AB_KNOBS compiles in the environment knobs of csrc/mjsim.hip (MJS_LDS_PAD, MJS_BP_EPG, MJS_BG_EPW: read once per
   mjs_create, a value out of range is an error). The shipped library has none and never reads the process environment.
-  --flag=-DMJS_STAMPS compiles in the phase stamps and the report of csrc/mjs_stamps_report.h."""
+  --flag=-DMJS_STAMPS compiles in the phase stamps and the report of csrc/mjs_stamps_report.h; with --flag=-DMJS_MASK_COUNTERS as well,
+  Robot-Reach's clamp-mask counters (mjs_reach.h MJS_MASK_STATS; they disturb the phase stamps)."""
 import shutil
 import subprocess
 import sys
