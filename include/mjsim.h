@@ -429,6 +429,87 @@ typedef struct {
 int mjs_rollout_visual_actor(mjs_handle* h, const mjs_actor* actor, mjs_encoder* const enc[2], const double* obs0_dev, int32_t T,
                              const mjs_visual_rollout* roll, const mjs_outputs* out, void* stream);
 
+/* A replay buffer on the device (entry points added after abi 3; mjs_config and the number stay as they are): the blocks the two
+ * rollouts above write, turned into the transitions SAC learns from, and batches drawn from them. A restatement of SB3's
+ * ReplayBuffer.add / sample (stable_baselines3/common/buffers.py; buffer_size=200_000 in scripts/sb3/reach_sac.py:108-124) over a
+ * [T, N] block. The entry points are stateless: the storage is a descriptor of caller-owned device memory (csrc/mjs_replay.h).
+ *
+ * Row (t, n) of a block is a transition iff step_type[t, n] != MJS_STEP_FIRST under MJS_AUTORESET_NEXT_STEP (the step after a LAST
+ * returns FIRST with the action ignored, composer.Environment's auto-reset) and always under MJS_AUTORESET_SAME_STEP. It stores
+ *   obs      = (float) prev[n, obs_index[j]], prev = obs[t-1], obs0 for t = 0 (the rounding of the actor's own input)
+ *   next_obs = the same columns of obs[t]; under same-step auto-reset, where terminated | truncated, of terminal_obs[t]
+ *   action   = squashed_actions[t, n]        reward = (float) reward[t, n]
+ *   done     = terminated ? 1.0f : 0.0f      (SB3's dones * (1 - timeouts); dmc2gym.py:144-145)      timeout = truncated
+ *   rgb[c]   = frame t of camera c, next_rgb[c] = frame t + 1, final_rgb[c] for t = T - 1 (frames are taken BEFORE the action)
+ * The r-th transition of a block in (t, n) order goes to ring row (count + r) % capacity, count = *cursor_dev = the number of
+ * transitions ever added; afterwards count += the block's transitions. Neither entry point reads anything back to the host or
+ * synchronises. */
+#define MJS_REPLAY_MAX_OBS 64
+#define MJS_REPLAY_MAX_CAMERAS 2
+typedef struct {
+  uint32_t struct_size;      /* sizeof(mjs_replay_storage), validated like mjs_config's */
+  int32_t device;            /* HIP device ordinal */
+  int32_t capacity;          /* ring rows: >= 1 */
+  int32_t obs_dim;           /* D, stored observation columns: 0..64 */
+  int32_t action_dim;        /* 1..8 */
+  int32_t n_cameras;         /* 0..2 */
+  int32_t height, width;     /* of the frames; positive where n_cameras > 0 */
+  uint64_t* cursor_dev;      /* one uint64: transitions ever added */
+  float* obs;                /* [capacity, D] (may be NULL where D == 0, like next_obs) */
+  float* next_obs;           /* [capacity, D] */
+  float* actions;            /* [capacity, action_dim] */
+  float* rewards;            /* [capacity] */
+  float* dones;              /* [capacity] */
+  uint8_t* timeouts;         /* [capacity] */
+  uint8_t* rgb[2];           /* [capacity, height, width, 3] for every camera c < n_cameras */
+  uint8_t* next_rgb[2];
+} mjs_replay_storage;        /* 120 bytes */
+typedef struct {
+  uint32_t struct_size;            /* sizeof(mjs_replay_block) */
+  int32_t T, N;                    /* control steps and envs of the block */
+  int32_t src_dim;                 /* width of a row of obs0 / obs / terminal_obs */
+  int32_t autoreset;               /* MJS_AUTORESET_NEXT_STEP or MJS_AUTORESET_SAME_STEP, the mode the block was made under */
+  int32_t reserved0;               /* 0 */
+  const int32_t* obs_index;        /* HOST [D]: the source column of stored column j, each 0..src_dim-1; copied during the call */
+  const double* obs0;              /* [N, src_dim]: the observation the first actor launch read */
+  const double* obs;               /* [T, N, src_dim] */
+  const double* terminal_obs;      /* [T, N, src_dim]: required under same-step auto-reset, ignored otherwise */
+  const double* reward;            /* [T, N] */
+  const uint8_t* terminated;       /* [T, N] */
+  const uint8_t* truncated;        /* [T, N] */
+  const uint8_t* step_type;        /* [T, N]: required under next-step auto-reset */
+  const float* squashed_actions;   /* [T, N, action_dim] */
+  const uint8_t* rgb[2];           /* [T, N, height, width, 3] for every camera of the storage */
+  const uint8_t* final_rgb[2];     /* [N, height, width, 3]: the frame after the block's last step */
+} mjs_replay_block;                /* 128 bytes */
+typedef struct {
+  uint32_t struct_size;      /* sizeof(mjs_replay_batch) */
+  int32_t reserved0;         /* 0 */
+  int64_t* idx_out;          /* [B]: the ring rows gathered; like every pointer below it may be NULL (that output is skipped) */
+  float* obs;                /* [B, D] */
+  float* next_obs;           /* [B, D] */
+  float* actions;            /* [B, action_dim] */
+  float* rewards;            /* [B] */
+  float* dones;              /* [B] */
+  uint8_t* timeouts;         /* [B] */
+  uint8_t* rgb[2];           /* [B, height, width, 3] */
+  uint8_t* next_rgb[2];
+} mjs_replay_batch;          /* 96 bytes */
+/* bytes of the workspace mjs_replay_add needs for a block of T x N rows (chunk counts and every row's ring row); 0 for a bad argument */
+uint64_t mjs_replay_workspace_bytes(int32_t T, int32_t N);
+/* Appends a block's transitions: three launches on the caller's stream, a fourth with cameras. workspace_dev:
+ * mjs_replay_workspace_bytes(T, N) bytes, 16-byte aligned, overwritten. MJS_ERR_INVALID_ARG (nothing launched, text in
+ * mjs_last_error(NULL)) for a null argument or required pointer, a wrong struct_size, capacity < 1, T * N > capacity, obs_dim,
+ * action_dim or n_cameras out of range, cameras without a positive size, src_dim < 1, an obs_index entry outside the source row,
+ * MJS_AUTORESET_DISABLED (or no mode at all), cameras under same-step auto-reset (the terminal frame does not exist there), same-step
+ * auto-reset without terminal_obs, T < 0 or N < 1. T == 0 does nothing and returns 0. */
+int mjs_replay_add(const mjs_replay_storage* storage, const mjs_replay_block* block, void* workspace_dev, void* stream);
+/* Gathers ring rows draws_dev[b] % min(count, capacity) into the outputs given, and the rows used into idx_out: two launches at most.
+ * draws_dev: non-negative int64 [B] on the device. While the buffer is empty idx_out is -1 and every output row zero.
+ * MJS_ERR_INVALID_ARG (nothing launched) for a null argument, a wrong struct_size, a storage mjs_replay_add would refuse or B < 0;
+ * B == 0 does nothing and returns 0. */
+int mjs_replay_sample(const mjs_replay_storage* storage, const int64_t* draws_dev, int32_t B, const mjs_replay_batch* out, void* stream);
+
 /* Replaces the Robot entity's control API on a stand-alone UR5e (entities/robots/robot.py:198-272): Robot.moveJ :211-216,
  * Robot.movej_IK :198-209, Robot.servoL :218-225, Robot.servoJ :227-259, then n_substeps x (Robot.before_substep :261-272 +
  * JointTrajectory.get_target_joint_positions joint_trajectory.py:41-47; Physics.step), then Robot.get_tcp_pose :153-168.

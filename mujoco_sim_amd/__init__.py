@@ -20,6 +20,7 @@ from .environments.tasks.robot_push_button import RobotPushButtonTask
 from .environments.tasks.robot_planar_push import RobotPushConfig, RobotPushTask
 from .policies import DeviceActor, DeviceEncoder  # noqa: F401
 from .recording import LeRobotDatasetRecorder  # noqa: F401
+from .replay import DeviceReplayBuffer  # noqa: F401
 from .vector_env import TASKS, HipVectorEnv  # noqa: F401
 
 __version__ = "0.1.0"

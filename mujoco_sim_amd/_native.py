@@ -39,6 +39,7 @@ ACTIVATION_RELU, ACTIVATION_TANH = 0, 1
 ACTOR_VARIANT_DEFAULT, ACTOR_VARIANT_TILE32 = 0, 1
 ACTOR_MAX_IN, ACTOR_MAX_HIDDEN, ACTOR_MAX_LAYERS, ACTOR_MAX_ACTIONS = 64, 256, 3, 8  # the limits mjs_actor_create checks
 ENCODER_MIN_SIZE, ENCODER_MAX_SIZE, ENCODER_MAX_FEATURES, ACTOR_MAX_BLOCKS = 36, 96, 512, 2  # the limits mjs_encoder_create / mjs_actor_create_visual check
+REPLAY_MAX_OBS, REPLAY_MAX_CAMERAS = 64, 2  # the limits mjs_replay_add checks (with ACTOR_MAX_ACTIONS)
 
 EXPORTED_SYMBOLS = [
     "mjs_version", "mjs_obs_dim", "mjs_action_dim", "mjs_action_dim_for", "mjs_state_dim", "mjs_env_obs_dim", "mjs_env_state_dim", "mjs_algorithmic_bytes_per_env_step", "mjs_env_algorithmic_bytes_per_env_step", "mjs_substeps",
@@ -48,6 +49,7 @@ EXPORTED_SYMBOLS = [
     "mjs_actor_create", "mjs_actor_destroy", "mjs_actor_load", "mjs_actor_actions", "mjs_rollout_actor",
     "mjs_encoder_create", "mjs_encoder_destroy", "mjs_encoder_load", "mjs_encoder_flat_dim", "mjs_encoder_workspace_bytes", "mjs_encoder_features",
     "mjs_actor_create_visual", "mjs_actor_actions_visual", "mjs_rollout_visual_actor",
+    "mjs_replay_workspace_bytes", "mjs_replay_add", "mjs_replay_sample",
 ]
 
 
@@ -145,6 +147,29 @@ class MjsVisualRollout(_Sized):
     _fields_ = [("struct_size", C.c_uint32), ("reserved0", C.c_int32), ("z_dev", C.c_void_p), ("low", C.POINTER(C.c_double)), ("high", C.POINTER(C.c_double)),
                 ("actions_out_dev", C.c_void_p), ("squashed_out_dev", C.c_void_p), ("scene_rgb_dev", C.c_void_p), ("wrist_rgb_dev", C.c_void_p),
                 ("scene_scratch_dev", C.c_void_p), ("wrist_scratch_dev", C.c_void_p), ("features_dev", C.c_void_p * 2), ("workspace_dev", C.c_void_p)]
+
+
+class MjsReplayStorage(_Sized):
+    """mjs_replay_storage: a replay ring as DEVICE pointers to caller-owned tensors, and its device cursor."""
+    _fields_ = [("struct_size", C.c_uint32), ("device", C.c_int32), ("capacity", C.c_int32), ("obs_dim", C.c_int32), ("action_dim", C.c_int32),
+                ("n_cameras", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("cursor_dev", C.c_void_p), ("obs", C.c_void_p),
+                ("next_obs", C.c_void_p), ("actions", C.c_void_p), ("rewards", C.c_void_p), ("dones", C.c_void_p), ("timeouts", C.c_void_p),
+                ("rgb", C.c_void_p * 2), ("next_rgb", C.c_void_p * 2)]
+
+
+class MjsReplayBlock(_Sized):
+    """mjs_replay_block: a [T, N] rollout block as DEVICE pointers; obs_index is a HOST int32 array (copied during the call)."""
+    _fields_ = [("struct_size", C.c_uint32), ("T", C.c_int32), ("N", C.c_int32), ("src_dim", C.c_int32), ("autoreset", C.c_int32), ("reserved0", C.c_int32),
+                ("obs_index", C.POINTER(C.c_int32)), ("obs0", C.c_void_p), ("obs", C.c_void_p), ("terminal_obs", C.c_void_p), ("reward", C.c_void_p),
+                ("terminated", C.c_void_p), ("truncated", C.c_void_p), ("step_type", C.c_void_p), ("squashed_actions", C.c_void_p),
+                ("rgb", C.c_void_p * 2), ("final_rgb", C.c_void_p * 2)]
+
+
+class MjsReplayBatch(_Sized):
+    """mjs_replay_batch: where mjs_replay_sample writes; a NULL output is skipped."""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved0", C.c_int32), ("idx_out", C.c_void_p), ("obs", C.c_void_p), ("next_obs", C.c_void_p),
+                ("actions", C.c_void_p), ("rewards", C.c_void_p), ("dones", C.c_void_p), ("timeouts", C.c_void_p), ("rgb", C.c_void_p * 2),
+                ("next_rgb", C.c_void_p * 2)]
 
 
 class MjsError(RuntimeError):
@@ -274,6 +299,10 @@ def lib() -> C.CDLL:
                                            C.c_void_p, C.c_void_p, C.c_void_p]
     L.mjs_rollout_visual_actor.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p * 2), C.c_void_p, C.c_int32, C.POINTER(MjsVisualRollout), C.POINTER(MjsOutputs),
                                            C.c_void_p]
+    L.mjs_replay_workspace_bytes.argtypes = [C.c_int32, C.c_int32]
+    L.mjs_replay_workspace_bytes.restype = C.c_uint64
+    L.mjs_replay_add.argtypes = [C.POINTER(MjsReplayStorage), C.POINTER(MjsReplayBlock), C.c_void_p, C.c_void_p]
+    L.mjs_replay_sample.argtypes = [C.POINTER(MjsReplayStorage), C.c_void_p, C.c_int32, C.POINTER(MjsReplayBatch), C.c_void_p]
     L.mjs_get_rng_state.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.mjs_set_rng_state.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = L

@@ -20,6 +20,7 @@
 #include "mjs_policy.h"
 #include "mjs_actor.h"
 #include "mjs_encoder.h"
+#include "mjs_replay.h"
 #ifdef MJS_STAMPS
 #include "mjs_stamps_report.h"
 #endif
@@ -1127,6 +1128,116 @@ int mjs_rollout_visual_actor(mjs_handle* h, const mjs_actor* actor, mjs_encoder*
     return launch_actor(h, actor, obs, roll->features_dev, roll->z_dev ? roll->z_dev + (size_t)t * NA : nullptr, roll->low, roll->high, actions,
                         roll->squashed_out_dev ? roll->squashed_out_dev + (size_t)t * NA : nullptr, s);
   });
+}
+
+// ---- replay buffer (mjs_replay.h) ---------------------------------------------------------------------------------------
+// what mjs_replay_add / mjs_replay_sample refuse about a storage descriptor; empty = fine
+static std::string replay_storage_refusal(const mjs_replay_storage* st) {
+  if (!st) return "storage is null";
+  if (st->struct_size != sizeof(mjs_replay_storage)) return "mjs_replay_storage.struct_size does not match this library's header";
+  if (st->capacity < 1) return "capacity must be at least 1";
+  if (st->obs_dim < 0 || st->obs_dim > rpl::MAX_D) return "obs_dim must be 0..64";
+  if (st->action_dim < 1 || st->action_dim > rpl::MAX_A) return "action_dim must be 1..8";
+  if (st->n_cameras < 0 || st->n_cameras > rpl::MAX_CAM) return "n_cameras must be 0..2";
+  if (st->n_cameras > 0 && (st->height < 1 || st->width < 1)) return "cameras need a positive height and width";
+  if (!st->cursor_dev) return "cursor_dev is null";
+  if (st->obs_dim > 0 && (!st->obs || !st->next_obs)) return "the storage's obs or next_obs is null";
+  if (!st->actions || !st->rewards || !st->dones || !st->timeouts) return "the storage's actions, rewards, dones or timeouts is null";
+  for (int c = 0; c < st->n_cameras; c++)
+    if (!st->rgb[c] || !st->next_rgb[c]) return "the storage's rgb or next_rgb of a camera is null";
+  return "";
+}
+
+uint64_t mjs_replay_workspace_bytes(int32_t T, int32_t N) { return T > 0 && N > 0 ? (uint64_t)rpl::ws_bytes((int64_t)T * N) : 0; }
+
+int mjs_replay_add(const mjs_replay_storage* st, const mjs_replay_block* blk, void* workspace_dev, void* stream) {
+  const auto refuse = [](const std::string& why) { return fail(nullptr, MJS_ERR_INVALID_ARG, "mjs_replay_add: " + why); };
+  if (std::string why = replay_storage_refusal(st); !why.empty()) return refuse(why);
+  if (!blk) return refuse("block is null");
+  if (blk->struct_size != sizeof(mjs_replay_block)) return refuse("mjs_replay_block.struct_size does not match this library's header");
+  if (blk->T < 0) return refuse("T is negative");
+  if (blk->N < 1) return refuse("N must be positive");
+  if (blk->autoreset != MJS_AUTORESET_NEXT_STEP && blk->autoreset != MJS_AUTORESET_SAME_STEP)
+    return refuse("the block's autoreset must be next-step or same-step (with auto-reset disabled a finished env stops producing transitions)");
+  const bool same_step = blk->autoreset == MJS_AUTORESET_SAME_STEP;
+  if (same_step && st->n_cameras > 0) return refuse("images under same-step auto-reset: the frame of the terminal state does not exist");
+  if (blk->src_dim < 1) return refuse("src_dim must be positive");
+  if (st->obs_dim > 0 && !blk->obs_index) return refuse("obs_index is null");
+  for (int j = 0; j < st->obs_dim; j++)
+    if (blk->obs_index[j] < 0 || blk->obs_index[j] >= blk->src_dim) return refuse("an obs_index entry lies outside the source row");
+  const int64_t rows = (int64_t)blk->T * blk->N;
+  if (rows > st->capacity) return refuse("T * N exceeds the capacity");
+  if (blk->T == 0) return MJS_OK;
+  if (!blk->obs0 || !blk->obs || !blk->reward || !blk->terminated || !blk->truncated || !blk->squashed_actions)
+    return refuse("obs0, obs, reward, terminated, truncated or squashed_actions is null");
+  if (same_step && !blk->terminal_obs) return refuse("same-step auto-reset needs terminal_obs");
+  if (!same_step && !blk->step_type) return refuse("next-step auto-reset needs step_type");
+  for (int c = 0; c < st->n_cameras; c++)
+    if (!blk->rgb[c] || !blk->final_rgb[c]) return refuse("the block's rgb or final_rgb of a camera is null");
+  if (st->n_cameras > 0 && rows * rpl::THREADS >= ((int64_t)1 << 32)) return refuse("a block with images holds at most 2^24 - 1 rows");
+  if (!workspace_dev) return refuse("workspace_dev is null");
+  if (int rc = device_refusal("mjs_replay_add", st->device)) return rc;
+  DeviceGuard dev_(st->device);
+  HIP_TRY(nullptr, dev_.err);
+
+  rpl::AddParams p{};
+  p.rows = rows; p.T = blk->T; p.N = blk->N; p.src_dim = blk->src_dim; p.same_step = same_step;
+  p.D = st->obs_dim; p.A = st->action_dim; p.n_cam = st->n_cameras; p.capacity = st->capacity;
+  p.frame_bytes = (uint64_t)st->height * (uint64_t)st->width * 3;
+  p.cursor = reinterpret_cast<unsigned long long*>(st->cursor_dev);
+  unsigned char* ws = static_cast<unsigned char*>(workspace_dev);
+  p.base = reinterpret_cast<unsigned long long*>(ws);
+  p.offsets = reinterpret_cast<uint32_t*>(ws + rpl::WS_HEADER);
+  p.dest = reinterpret_cast<int32_t*>(ws + rpl::WS_HEADER + rpl::ws_offsets_bytes(rows));
+  p.obs0 = blk->obs0; p.obs = blk->obs; p.terminal_obs = blk->terminal_obs; p.reward = blk->reward;
+  p.terminated = blk->terminated; p.truncated = blk->truncated; p.step_type = blk->step_type; p.squashed = blk->squashed_actions;
+  p.s_obs = st->obs; p.s_next_obs = st->next_obs; p.s_actions = st->actions; p.s_rewards = st->rewards; p.s_dones = st->dones; p.s_timeouts = st->timeouts;
+  for (int c = 0; c < st->n_cameras; c++) {
+    p.rgb[c] = blk->rgb[c]; p.final_rgb[c] = blk->final_rgb[c]; p.s_rgb[c] = st->rgb[c]; p.s_next_rgb[c] = st->next_rgb[c];
+  }
+  for (int j = 0; j < st->obs_dim; j++) p.index.v[j] = blk->obs_index[j];
+  const hipStream_t s = (hipStream_t)stream;
+  const dim3 chunks((unsigned)rpl::n_chunks(rows));
+  rpl::count_kernel<<<chunks, rpl::THREADS, 0, s>>>(p);
+  rpl::scan_kernel<<<dim3(1), rpl::THREADS, 0, s>>>(p);
+  rpl::scatter_kernel<<<chunks, rpl::THREADS, 0, s>>>(p);
+  if (p.n_cam > 0) rpl::image_kernel<<<dim3((unsigned)rows), rpl::THREADS, 0, s>>>(p);
+  HIP_TRY(nullptr, hipGetLastError());
+  return MJS_OK;
+}
+
+int mjs_replay_sample(const mjs_replay_storage* st, const int64_t* draws_dev, int32_t B, const mjs_replay_batch* out, void* stream) {
+  const auto refuse = [](const std::string& why) { return fail(nullptr, MJS_ERR_INVALID_ARG, "mjs_replay_sample: " + why); };
+  if (std::string why = replay_storage_refusal(st); !why.empty()) return refuse(why);
+  if (!out) return refuse("out is null");
+  if (out->struct_size != sizeof(mjs_replay_batch)) return refuse("mjs_replay_batch.struct_size does not match this library's header");
+  if (B < 0) return refuse("B is negative");
+  if (B == 0) return MJS_OK;
+  if (!draws_dev) return refuse("draws_dev is null");
+  if (int rc = device_refusal("mjs_replay_sample", st->device)) return rc;
+  DeviceGuard dev_(st->device);
+  HIP_TRY(nullptr, dev_.err);
+
+  rpl::SampleParams p{};
+  p.B = B; p.D = st->obs_dim; p.A = st->action_dim; p.n_cam = st->n_cameras; p.capacity = st->capacity;
+  p.frame_bytes = (uint64_t)st->height * (uint64_t)st->width * 3;
+  p.cursor = reinterpret_cast<const unsigned long long*>(st->cursor_dev);
+  p.draws = draws_dev;
+  p.s_obs = st->obs; p.s_next_obs = st->next_obs; p.s_actions = st->actions; p.s_rewards = st->rewards; p.s_dones = st->dones; p.s_timeouts = st->timeouts;
+  p.idx_out = out->idx_out;
+  p.obs = st->obs_dim > 0 ? out->obs : nullptr; p.next_obs = st->obs_dim > 0 ? out->next_obs : nullptr;
+  p.actions = out->actions; p.rewards = out->rewards; p.dones = out->dones; p.timeouts = out->timeouts;
+  bool images = false;
+  for (int c = 0; c < st->n_cameras; c++) {
+    p.s_rgb[c] = st->rgb[c]; p.s_next_rgb[c] = st->next_rgb[c]; p.rgb[c] = out->rgb[c]; p.next_rgb[c] = out->next_rgb[c];
+    images = images || out->rgb[c] || out->next_rgb[c];
+  }
+  if (images && (int64_t)B * rpl::THREADS >= ((int64_t)1 << 32)) return refuse("a batch with images holds at most 2^24 - 1 rows");
+  const hipStream_t s = (hipStream_t)stream;
+  rpl::sample_kernel<<<dim3((unsigned)(((int64_t)B + rpl::SAMPLE_ROWS - 1) / rpl::SAMPLE_ROWS)), rpl::THREADS, 0, s>>>(p);
+  if (images) rpl::sample_image_kernel<<<dim3((unsigned)B), rpl::THREADS, 0, s>>>(p);
+  HIP_TRY(nullptr, hipGetLastError());
+  return MJS_OK;
 }
 
 // ---- cameras ------------------------------------------------------------------------------------------------------------
