@@ -510,6 +510,71 @@ int mjs_replay_add(const mjs_replay_storage* storage, const mjs_replay_block* bl
  * B == 0 does nothing and returns 0. */
 int mjs_replay_sample(const mjs_replay_storage* storage, const int64_t* draws_dev, int32_t B, const mjs_replay_batch* out, void* stream);
 
+/* SAC's critics and the no-gradient half of its update on the device (entry points added after abi 3; mjs_config and the number stay as
+ * they are): what stable_baselines3/sac/sac.py SAC.train computes first from a batch of mjs_replay_sample, under torch.no_grad(),
+ * with the twin Q networks of stable_baselines3/common/policies.py ContinuousCritic (csrc/mjs_critic.h), in float32 with float32
+ * accumulation like the actor above:
+ *   Q_c(o, a)   = W_head act(... act(W_0 [o | a] + b_0) ...) + b_head                       c < n_critics, one scalar per row
+ *   ls = clamp(log_std(next_obs), -20, 2)    u = mu(next_obs) + expf(ls) * z    a' = tanhf(u)
+ *   logp = sum_j (-0.5 z_j^2 - ls_j - 0.5 log(2 pi)) - sum_j logf(1 - a'_j^2 + 1e-6)         j = 0..action_dim-1 in order, then one subtraction
+ *   target = r + (1 - done) * gamma * (min_c Q_c(next_obs, a') - ent_coef * logp)            operation by operation, no contraction
+ * Nothing here takes a gradient. A critic belongs to a device, like an actor. */
+#define MJS_CRITIC_MAX 2
+typedef struct mjs_critic mjs_critic;
+typedef struct {
+  uint32_t struct_size;      /* sizeof(mjs_critic_desc), validated like mjs_config's */
+  int32_t device;            /* HIP device ordinal */
+  int32_t obs_dim;           /* D: 1..64 (MJS_REPLAY_MAX_OBS) */
+  int32_t action_dim;        /* A: 1..8; the first layer reads D + A columns */
+  int32_t n_critics;         /* 1..2 networks of one architecture */
+  int32_t n_hidden;          /* 1..3 */
+  int32_t hidden[3];         /* widths, each 1..256; entries past n_hidden are ignored */
+  int32_t activation;        /* MJS_ACTIVATION_* */
+} mjs_critic_desc;           /* 40 bytes */
+/* Allocates the packed weight buffers and nothing else. MJS_ERR_INVALID_ARG (text in mjs_last_error(NULL)) for a wrong struct_size,
+ * a null pointer or any field out of range. */
+int mjs_critic_create(const mjs_critic_desc* desc, mjs_critic** out);
+void mjs_critic_destroy(mjs_critic* critic);
+/* DEVICE pointers to float32 parameters in torch.nn.Linear layout, per critic c < n_critics (entries past it are ignored). */
+typedef struct {
+  uint32_t struct_size;          /* sizeof(mjs_critic_weights) */
+  int32_t reserved0;             /* 0 */
+  const float* hidden_w[2][3];   /* [c][l]: [hidden[l], l == 0 ? obs_dim + action_dim : hidden[l-1]]; layers past n_hidden are ignored */
+  const float* hidden_b[2][3];
+  const float* out_w[2];         /* [1, hidden[n_hidden-1]] */
+  const float* out_b[2];         /* [1] */
+} mjs_critic_weights;            /* 136 bytes */
+/* Blends the parameters into the critic's own K-major copy with small kernels on the caller's stream: copy = (1 - tau) * copy + tau *
+ * given, SB3's polyak_update done on the packed copy (its padding stays 0), so that a target critic needs no torch module. tau in
+ * (0, 1]; tau == 1 copies, and a first load must have tau == 1 (the copy is uninitialised before it): MJS_ERR_INVALID_ARG otherwise,
+ * as for a null pointer or a wrong struct_size. Never synchronises (the contract of mjs_actor_load). */
+int mjs_critic_load(mjs_critic* critic, const mjs_critic_weights* weights, double tau, void* stream);
+/* One launch: obs_dev float32 [B, obs_dim], actions_dev float32 [B, action_dim] -> q_out_dev float32 [n_critics, B]. No handle; the
+ * launch goes to the critic's device. MJS_ERR_INVALID_ARG (nothing launched) for a null pointer, B < 0 or a critic that was never
+ * loaded; B == 0 does nothing and returns 0. */
+int mjs_critic_q(const mjs_critic* critic, const float* obs_dev, const float* actions_dev, int32_t B, float* q_out_dev, void* stream);
+typedef struct {
+  uint32_t struct_size;          /* sizeof(mjs_td_target_args) */
+  int32_t B;                     /* batch rows: >= 0 */
+  const float* next_obs_dev;     /* [B, obs_dim], required: the actor's input columns in order (its obs_index plays no role) */
+  const float* rewards_dev;      /* [B], required */
+  const float* dones_dev;        /* [B], required: 1.0f where the episode terminated (mjs_replay_sample's dones) */
+  const float* z_dev;            /* [B, action_dim], required: standard-normal draws */
+  double gamma;                  /* 0..1, rounded to float32 */
+  double ent_coef;               /* rounded to float32; ignored where ent_coef_dev is given */
+  const float* ent_coef_dev;     /* one float32 on the device (SB3's learned coefficient), read by the kernel, or NULL */
+  float* target_out_dev;         /* [B], required */
+  float* next_actions_out_dev;   /* [B, action_dim] or NULL: a' */
+  float* next_log_prob_out_dev;  /* [B] or NULL: logp */
+  float* q_next_out_dev;         /* [n_critics, B] or NULL: Q_c(next_obs, a') before the min */
+} mjs_td_target_args;            /* 96 bytes */
+/* One launch for the whole block above (the actor's variant is ignored: 16 rows per workgroup). q_next_out_dev equals, bit for bit,
+ * what mjs_critic_q gives on (next_obs, next_actions_out_dev). MJS_ERR_INVALID_ARG (nothing launched, text in mjs_last_error(NULL)) for
+ * a null argument or required pointer, a wrong struct_size, B < 0, gamma outside [0, 1], an actor or critic that was never loaded,
+ * actor and critic of different devices, an actor of mjs_actor_create_visual, or an actor whose in_dim or action_dim is not the
+ * critic's obs_dim or action_dim. B == 0 does nothing and returns 0. */
+int mjs_sac_td_target(const mjs_actor* actor, const mjs_critic* critic, const mjs_td_target_args* args, void* stream);
+
 /* Replaces the Robot entity's control API on a stand-alone UR5e (entities/robots/robot.py:198-272): Robot.moveJ :211-216,
  * Robot.movej_IK :198-209, Robot.servoL :218-225, Robot.servoJ :227-259, then n_substeps x (Robot.before_substep :261-272 +
  * JointTrajectory.get_target_joint_positions joint_trajectory.py:41-47; Physics.step), then Robot.get_tcp_pose :153-168.

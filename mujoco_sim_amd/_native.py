@@ -40,6 +40,7 @@ ACTOR_VARIANT_DEFAULT, ACTOR_VARIANT_TILE32 = 0, 1
 ACTOR_MAX_IN, ACTOR_MAX_HIDDEN, ACTOR_MAX_LAYERS, ACTOR_MAX_ACTIONS = 64, 256, 3, 8  # the limits mjs_actor_create checks
 ENCODER_MIN_SIZE, ENCODER_MAX_SIZE, ENCODER_MAX_FEATURES, ACTOR_MAX_BLOCKS = 36, 96, 512, 2  # the limits mjs_encoder_create / mjs_actor_create_visual check
 REPLAY_MAX_OBS, REPLAY_MAX_CAMERAS = 64, 2  # the limits mjs_replay_add checks (with ACTOR_MAX_ACTIONS)
+CRITIC_MAX_OBS, CRITIC_MAX_CRITICS = REPLAY_MAX_OBS, 2  # the limits mjs_critic_create checks (with ACTOR_MAX_HIDDEN / _LAYERS / _ACTIONS)
 
 EXPORTED_SYMBOLS = [
     "mjs_version", "mjs_obs_dim", "mjs_action_dim", "mjs_action_dim_for", "mjs_state_dim", "mjs_env_obs_dim", "mjs_env_state_dim", "mjs_algorithmic_bytes_per_env_step", "mjs_env_algorithmic_bytes_per_env_step", "mjs_substeps",
@@ -50,6 +51,7 @@ EXPORTED_SYMBOLS = [
     "mjs_encoder_create", "mjs_encoder_destroy", "mjs_encoder_load", "mjs_encoder_flat_dim", "mjs_encoder_workspace_bytes", "mjs_encoder_features",
     "mjs_actor_create_visual", "mjs_actor_actions_visual", "mjs_rollout_visual_actor",
     "mjs_replay_workspace_bytes", "mjs_replay_add", "mjs_replay_sample",
+    "mjs_critic_create", "mjs_critic_destroy", "mjs_critic_load", "mjs_critic_q", "mjs_sac_td_target",
 ]
 
 
@@ -170,6 +172,25 @@ class MjsReplayBatch(_Sized):
     _fields_ = [("struct_size", C.c_uint32), ("reserved0", C.c_int32), ("idx_out", C.c_void_p), ("obs", C.c_void_p), ("next_obs", C.c_void_p),
                 ("actions", C.c_void_p), ("rewards", C.c_void_p), ("dones", C.c_void_p), ("timeouts", C.c_void_p), ("rgb", C.c_void_p * 2),
                 ("next_rgb", C.c_void_p * 2)]
+
+
+class MjsCriticDesc(_Sized):
+    """mjs_critic_desc: the shape of SAC's critics (n_critics networks of one architecture over [obs | action])."""
+    _fields_ = [("struct_size", C.c_uint32), ("device", C.c_int32), ("obs_dim", C.c_int32), ("action_dim", C.c_int32), ("n_critics", C.c_int32),
+                ("n_hidden", C.c_int32), ("hidden", C.c_int32 * 3), ("activation", C.c_int32)]
+
+
+class MjsCriticWeights(_Sized):
+    """mjs_critic_weights: DEVICE pointers to float32 parameters in torch.nn.Linear layout, [critic][layer]."""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved0", C.c_int32), ("hidden_w", C.c_void_p * 3 * 2), ("hidden_b", C.c_void_p * 3 * 2),
+                ("out_w", C.c_void_p * 2), ("out_b", C.c_void_p * 2)]
+
+
+class MjsTdTargetArgs(_Sized):
+    """mjs_td_target_args: a batch's DEVICE tensors, the discount and entropy coefficient, and where mjs_sac_td_target writes."""
+    _fields_ = [("struct_size", C.c_uint32), ("B", C.c_int32), ("next_obs_dev", C.c_void_p), ("rewards_dev", C.c_void_p), ("dones_dev", C.c_void_p),
+                ("z_dev", C.c_void_p), ("gamma", C.c_double), ("ent_coef", C.c_double), ("ent_coef_dev", C.c_void_p), ("target_out_dev", C.c_void_p),
+                ("next_actions_out_dev", C.c_void_p), ("next_log_prob_out_dev", C.c_void_p), ("q_next_out_dev", C.c_void_p)]
 
 
 class MjsError(RuntimeError):
@@ -303,6 +324,12 @@ def lib() -> C.CDLL:
     L.mjs_replay_workspace_bytes.restype = C.c_uint64
     L.mjs_replay_add.argtypes = [C.POINTER(MjsReplayStorage), C.POINTER(MjsReplayBlock), C.c_void_p, C.c_void_p]
     L.mjs_replay_sample.argtypes = [C.POINTER(MjsReplayStorage), C.c_void_p, C.c_int32, C.POINTER(MjsReplayBatch), C.c_void_p]
+    L.mjs_critic_create.argtypes = [C.POINTER(MjsCriticDesc), C.POINTER(C.c_void_p)]
+    L.mjs_critic_destroy.argtypes = [C.c_void_p]
+    L.mjs_critic_destroy.restype = None
+    L.mjs_critic_load.argtypes = [C.c_void_p, C.POINTER(MjsCriticWeights), C.c_double, C.c_void_p]
+    L.mjs_critic_q.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    L.mjs_sac_td_target.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(MjsTdTargetArgs), C.c_void_p]
     L.mjs_get_rng_state.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.mjs_set_rng_state.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = L

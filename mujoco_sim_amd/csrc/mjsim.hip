@@ -21,6 +21,7 @@
 #include "mjs_actor.h"
 #include "mjs_encoder.h"
 #include "mjs_replay.h"
+#include "mjs_critic.h"
 #ifdef MJS_STAMPS
 #include "mjs_stamps_report.h"
 #endif
@@ -138,6 +139,16 @@ struct mjs_actor {
   bool visual = false;
   int in_total = 0;                // desc.in_dim + the blocks' widths: the first layer's fan-in
   int block_width[act::MAX_BLOCKS] = {0, 0};
+};
+
+// SAC's critics (mjs_critic.h): the shape, and the library's packed copy of every network's parameters.
+struct mjs_critic {
+  mjs_critic_desc desc;
+  int k0 = 0, width[3] = {0, 0, 0};  // obs_dim + action_dim padded to act::KPAD, hidden widths padded to act::OPAD
+  int widest = 0;                    // of k0, width[], act::OPAD
+  float* w[crit::MAX_CRITICS][4] = {};  // packed [k][out] per critic: hidden layers, then (slot 3) the scalar head padded to act::OPAD
+  float* b[crit::MAX_CRITICS][4] = {};
+  bool loaded = false;               // mjs_critic_load has run
 };
 
 // An image encoder (mjs_encoder.h): the geometry, and the library's packed copy of the parameters. No per-handle state.
@@ -1236,6 +1247,160 @@ int mjs_replay_sample(const mjs_replay_storage* st, const int64_t* draws_dev, in
   const hipStream_t s = (hipStream_t)stream;
   rpl::sample_kernel<<<dim3((unsigned)(((int64_t)B + rpl::SAMPLE_ROWS - 1) / rpl::SAMPLE_ROWS)), rpl::THREADS, 0, s>>>(p);
   if (images) rpl::sample_image_kernel<<<dim3((unsigned)B), rpl::THREADS, 0, s>>>(p);
+  HIP_TRY(nullptr, hipGetLastError());
+  return MJS_OK;
+}
+
+// ---- SAC's critics and the fused TD target (mjs_critic.h) ---------------------------------------------------------------------
+int mjs_critic_create(const mjs_critic_desc* desc, mjs_critic** out) {
+  const std::string name = "mjs_critic_create";
+  if (!desc || !out) return fail(nullptr, MJS_ERR_INVALID_ARG, name + ": null argument");
+  *out = nullptr;
+  if (desc->struct_size != sizeof(mjs_critic_desc))
+    return fail(nullptr, MJS_ERR_INVALID_ARG, name + ": mjs_critic_desc.struct_size does not match this library's header");
+  if (desc->obs_dim < 1 || desc->obs_dim > crit::MAX_OBS) return fail(nullptr, MJS_ERR_INVALID_ARG, name + ": obs_dim must be 1..64");
+  if (desc->action_dim < 1 || desc->action_dim > crit::MAX_ACT) return fail(nullptr, MJS_ERR_INVALID_ARG, name + ": action_dim must be 1..8");
+  if (desc->n_critics < 1 || desc->n_critics > crit::MAX_CRITICS) return fail(nullptr, MJS_ERR_INVALID_ARG, name + ": n_critics must be 1..2");
+  if (desc->n_hidden < 1 || desc->n_hidden > act::MAX_LAYERS) return fail(nullptr, MJS_ERR_INVALID_ARG, name + ": n_hidden must be 1..3");
+  for (int l = 0; l < desc->n_hidden; l++)
+    if (desc->hidden[l] < 1 || desc->hidden[l] > act::MAX_HIDDEN) return fail(nullptr, MJS_ERR_INVALID_ARG, name + ": every hidden width must be 1..256");
+  if (desc->activation != MJS_ACTIVATION_RELU && desc->activation != MJS_ACTIVATION_TANH) return fail(nullptr, MJS_ERR_INVALID_ARG, name + ": bad activation");
+  if (int rc = device_refusal(name, desc->device)) return rc;
+  DeviceGuard dev_(desc->device);
+  std::unique_ptr<mjs_critic, void (*)(mjs_critic*)> guard(new (std::nothrow) mjs_critic(), mjs_critic_destroy);
+  mjs_critic* q = guard.get();
+  if (!q) return fail(nullptr, MJS_ERR_ALLOC, name + ": out of host memory");
+  CREATE_TRY(name, dev_.err);
+  q->desc = *desc;
+  q->k0 = act::round_up(desc->obs_dim + desc->action_dim, act::KPAD);
+  q->widest = q->k0 > act::OPAD ? q->k0 : act::OPAD;
+  for (int l = 0; l < desc->n_hidden; l++) {
+    q->width[l] = act::round_up(desc->hidden[l], act::OPAD);
+    q->widest = q->width[l] > q->widest ? q->width[l] : q->widest;
+  }
+  for (int c = 0; c < desc->n_critics; c++) {
+    int K = q->k0;
+    for (int l = 0; l < desc->n_hidden; l++) {
+      CREATE_TRY(name, hipMalloc(&q->w[c][l], sizeof(float) * (size_t)K * q->width[l]));
+      CREATE_TRY(name, hipMalloc(&q->b[c][l], sizeof(float) * q->width[l]));
+      K = q->width[l];
+    }
+    CREATE_TRY(name, hipMalloc(&q->w[c][3], sizeof(float) * (size_t)K * act::OPAD));
+    CREATE_TRY(name, hipMalloc(&q->b[c][3], sizeof(float) * act::OPAD));
+  }
+  // three images of the widest stride any actor / critic pair can ask for stay below the 64 KB no kernel needs an opt-in for
+  static_assert(crit::MAX_K0 <= act::MAX_HIDDEN && crit::lds_bytes(act::MAX_HIDDEN) <= 64 * 1024, "LDS images of the critic kernels");
+  *out = guard.release();
+  return MJS_OK;
+}
+
+void mjs_critic_destroy(mjs_critic* q) {
+  if (!q) return;
+  for (int c = 0; c < crit::MAX_CRITICS; c++) free_all({q->w[c][0], q->w[c][1], q->w[c][2], q->w[c][3], q->b[c][0], q->b[c][1], q->b[c][2], q->b[c][3]});
+  delete q;
+}
+
+int mjs_critic_load(mjs_critic* q, const mjs_critic_weights* wts, double tau, void* stream) {
+  const auto refuse = [](const std::string& why) { return fail(nullptr, MJS_ERR_INVALID_ARG, "mjs_critic_load: " + why); };
+  if (!q || !wts) return refuse("null argument");
+  if (wts->struct_size != sizeof(mjs_critic_weights)) return refuse("mjs_critic_weights.struct_size does not match this library's header");
+  if (!(tau > 0.0 && tau <= 1.0)) return refuse("tau must lie in (0, 1]");
+  if (!q->loaded && tau != 1.0) return refuse("a first load must have tau == 1 (there is nothing to blend with yet)");
+  for (int c = 0; c < q->desc.n_critics; c++) {
+    for (int l = 0; l < q->desc.n_hidden; l++)
+      if (!wts->hidden_w[c][l] || !wts->hidden_b[c][l]) return refuse("a hidden layer's weight or bias is null");
+    if (!wts->out_w[c] || !wts->out_b[c]) return refuse("a head's weight or bias is null");
+  }
+  DeviceGuard dev_(q->desc.device);
+  HIP_TRY(nullptr, dev_.err);
+  for (int c = 0; c < q->desc.n_critics; c++) {
+    int in = q->desc.obs_dim + q->desc.action_dim, K = q->k0;
+    for (int l = 0; l <= q->desc.n_hidden; l++) {
+      const bool head = l == q->desc.n_hidden;
+      act::PackParams p;
+      p.w0 = head ? wts->out_w[c] : wts->hidden_w[c][l];
+      p.b0 = head ? wts->out_b[c] : wts->hidden_b[c][l];
+      p.w1 = p.b1 = nullptr;
+      p.out0 = head ? 1 : q->desc.hidden[l];
+      p.out1 = 0;
+      p.in = in;
+      p.K = K;
+      p.O = head ? act::OPAD : q->width[l];
+      p.dst_w = q->w[c][head ? 3 : l];
+      p.dst_b = q->b[c][head ? 3 : l];
+      const dim3 grid((unsigned)((p.K * p.O + 255) / 256));
+      if (tau == 1.0) act::pack_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(p);  // the plain copy: never reads the destination
+      else crit::pack_lerp_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(p, (float)(1.0 - tau), (float)tau);
+      if (!head) { in = q->desc.hidden[l]; K = q->width[l]; }
+    }
+  }
+  HIP_TRY(nullptr, hipGetLastError());
+  q->loaded = true;
+  return MJS_OK;
+}
+
+// the kernels' view of one packed network: a critic's copy c, or (critic nullptr) the actor's
+static crit::Mlp mlp_of(const mjs_critic* q, int c, const mjs_actor* a) {
+  crit::Mlp m;
+  float* const* w = q ? q->w[c] : a->w;
+  float* const* b = q ? q->b[c] : a->b;
+  const int* width = q ? q->width : a->width;
+  m.W0 = w[0]; m.W1 = w[1]; m.W2 = w[2]; m.WH = w[3];
+  m.B0 = b[0]; m.B1 = b[1]; m.B2 = b[2]; m.BH = b[3];
+  m.n_hidden = q ? q->desc.n_hidden : a->desc.n_hidden;
+  m.k0 = q ? q->k0 : a->k0;
+  m.w0 = width[0]; m.w1 = width[1]; m.w2 = width[2];
+  m.activation = (q ? q->desc.activation : a->desc.activation) == MJS_ACTIVATION_TANH ? act::ACT_TANH : act::ACT_RELU;
+  return m;
+}
+static crit::CriticParams critic_params(const mjs_critic* q, int32_t B, int widest) {
+  crit::CriticParams p{};
+  p.B = B; p.D = q->desc.obs_dim; p.A = q->desc.action_dim; p.n_critics = q->desc.n_critics;
+  p.S = act::lds_stride(widest);
+  for (int c = 0; c < q->desc.n_critics; c++) p.net[c] = mlp_of(q, c, nullptr);
+  return p;
+}
+
+int mjs_critic_q(const mjs_critic* q, const float* obs_dev, const float* actions_dev, int32_t B, float* q_out_dev, void* stream) {
+  const auto refuse = [](const std::string& why) { return fail(nullptr, MJS_ERR_INVALID_ARG, "mjs_critic_q: " + why); };
+  if (!q) return refuse("critic is null");
+  if (!q->loaded) return refuse("the critic has no parameters yet (mjs_critic_load)");
+  if (B < 0) return refuse("B is negative");
+  if (B == 0) return MJS_OK;
+  if (!obs_dev || !actions_dev || !q_out_dev) return refuse("obs_dev, actions_dev or q_out_dev is null");
+  DeviceGuard dev_(q->desc.device);
+  HIP_TRY(nullptr, dev_.err);
+  const crit::CriticParams p = critic_params(q, B, q->widest);
+  crit::q_kernel<<<dim3((unsigned)(((int64_t)B + crit::ROWS - 1) / crit::ROWS)), act::WAVES * 64, crit::lds_bytes(q->widest), (hipStream_t)stream>>>(p, obs_dev, actions_dev, q_out_dev);
+  HIP_TRY(nullptr, hipGetLastError());
+  return MJS_OK;
+}
+
+int mjs_sac_td_target(const mjs_actor* actor, const mjs_critic* q, const mjs_td_target_args* args, void* stream) {
+  const auto refuse = [](const std::string& why) { return fail(nullptr, MJS_ERR_INVALID_ARG, "mjs_sac_td_target: " + why); };
+  if (!actor || !q || !args) return refuse("actor, critic or args is null");
+  if (args->struct_size != sizeof(mjs_td_target_args)) return refuse("mjs_td_target_args.struct_size does not match this library's header");
+  if (actor->visual) return refuse("the actor reads feature blocks (mjs_actor_create_visual): visual critics are not built");
+  if (actor->desc.device != q->desc.device) return refuse("the actor lives on another device than the critic");
+  if (!actor->loaded) return refuse("the actor has no parameters yet (mjs_actor_load)");
+  if (!q->loaded) return refuse("the critic has no parameters yet (mjs_critic_load)");
+  if (actor->desc.in_dim != q->desc.obs_dim) return refuse("the actor's in_dim is not the critic's obs_dim");
+  if (actor->desc.action_dim != q->desc.action_dim) return refuse("the actor's action_dim is not the critic's");
+  if (args->B < 0) return refuse("B is negative");
+  if (!(args->gamma >= 0.0 && args->gamma <= 1.0)) return refuse("gamma must lie in [0, 1]");
+  if (args->B == 0) return MJS_OK;
+  if (!args->next_obs_dev || !args->rewards_dev || !args->dones_dev || !args->z_dev || !args->target_out_dev)
+    return refuse("next_obs_dev, rewards_dev, dones_dev, z_dev or target_out_dev is null");
+  DeviceGuard dev_(q->desc.device);
+  HIP_TRY(nullptr, dev_.err);
+  const int widest = actor->widest > q->widest ? actor->widest : q->widest;  // one stride for the actor's and the critics' layers
+  crit::TdParams p{};
+  p.c = critic_params(q, args->B, widest);
+  p.actor = mlp_of(nullptr, 0, actor);
+  p.next_obs = args->next_obs_dev; p.rewards = args->rewards_dev; p.dones = args->dones_dev; p.z = args->z_dev;
+  p.gamma = (float)args->gamma; p.ent_coef = (float)args->ent_coef; p.ent_coef_dev = args->ent_coef_dev;
+  p.target = args->target_out_dev; p.next_actions = args->next_actions_out_dev; p.next_log_prob = args->next_log_prob_out_dev; p.q_next = args->q_next_out_dev;
+  crit::td_target_kernel<<<dim3((unsigned)(((int64_t)args->B + crit::ROWS - 1) / crit::ROWS)), act::WAVES * 64, crit::lds_bytes(widest), (hipStream_t)stream>>>(p);
   HIP_TRY(nullptr, hipGetLastError());
   return MJS_OK;
 }

@@ -432,3 +432,238 @@ class DeviceActor(_NativeObject):
         super().close()
         for e in getattr(self, "_owned_encoders", ()):
             e.close()
+
+
+class DeviceCritic(_NativeObject):
+    """SAC's critics (SB3's ``ContinuousCritic``: ``n_critics`` MLPs over ``[obs | action]`` with a scalar head) held by libmjsim.so
+    for one device (csrc/mjs_critic.h). Forward only: :meth:`q_values` and :func:`sac_td_target` take no gradient; the critic and
+    actor losses stay in torch. float32 with float32 accumulation, like :class:`DeviceActor`.
+
+    The object keeps references to the torch modules it was made from; :meth:`load` packs their CURRENT parameters, or blends those
+    of other modules of the same shapes into the packed copy (``tau < 1``: SB3's ``polyak_update``), so that a TARGET critic can
+    live in the library alone: ``target = DeviceCritic.from_sb3(critic)`` once, ``target.load(critic_q_nets, tau=0.005)`` per
+    gradient step."""
+    _handle, _destroy = "_q", "mjs_critic_destroy"
+
+    def __init__(self, device, obs_dim, action_dim, q_nets, activation="relu"):
+        self._q = None
+        if activation not in _ACTIVATION_IDS:
+            raise ValueError(f"activation must be one of {sorted(_ACTIVATION_IDS)}, got {activation!r}")
+        self.activation = activation
+        self.obs_dim, self.action_dim = int(obs_dim), int(action_dim)
+        if not 1 <= self.obs_dim <= nat.CRITIC_MAX_OBS:
+            raise ValueError(f"a critic reads 1..{nat.CRITIC_MAX_OBS} observation columns, got {self.obs_dim}")
+        if not 1 <= self.action_dim <= nat.ACTOR_MAX_ACTIONS:
+            raise ValueError(f"a critic reads 1..{nat.ACTOR_MAX_ACTIONS} action components, got {self.action_dim}")
+        self.device = torch.device(device if not isinstance(device, int) else f"cuda:{device}")
+        self.q_nets = self._as_nets(q_nets)
+        self.n_critics = len(self.q_nets)
+        self.widths = [int(m.out_features) for m in self.q_nets[0][:-1]]
+        if not 1 <= len(self.widths) <= nat.ACTOR_MAX_LAYERS:
+            raise ValueError(f"a critic has 1..{nat.ACTOR_MAX_LAYERS} hidden layers, got {len(self.widths)}")
+        self._check_modules(self.q_nets)
+        if self.device.type == "cuda" and self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self._dev_index = self.device.index or 0
+        # ---- native from here on
+        self._lib = nat.lib()
+        desc = nat.MjsCriticDesc(device=self._dev_index, obs_dim=self.obs_dim, action_dim=self.action_dim, n_critics=self.n_critics,
+                                 n_hidden=len(self.widths), hidden=(C.c_int32 * 3)(*self.widths), activation=_ACTIVATION_IDS[activation])
+        q = C.c_void_p()
+        nat.check(self._lib.mjs_critic_create(C.byref(desc), C.byref(q)))
+        self._q = q
+        self._staged = ()
+        self._loaded = False
+        self.load()
+
+    @classmethod
+    def from_linears(cls, device, obs_dim, action_dim, q_nets, activation="relu"):
+        """``q_nets``: 1..2 sequences of ``torch.nn.Linear``, each ``(hidden..., out)`` with 1..3 hidden layers of width 1..256, the
+        first reading ``obs_dim + action_dim`` columns (``obs_dim`` 1..64, ``action_dim`` 1..8), ``out`` a ``Linear(., 1)``; all
+        critics of one architecture, float32 on ``device``. ``ValueError`` for anything else, before any native call."""
+        return cls(device, obs_dim, action_dim, q_nets, activation=activation)
+
+    @classmethod
+    def from_sb3(cls, critic, action_dim=None):
+        """From an object shaped like ``stable_baselines3.common.policies.ContinuousCritic``: ``critic.q_networks`` a list of
+        ``nn.Sequential`` of ``Linear`` / activation (``ReLU`` or ``Tanh``, one kind) ... ``Linear(., 1)``. ``action_dim`` defaults to
+        ``critic.action_space.shape[0]``; the rest of the first layer's inputs are observation columns (the features extractor is not
+        evaluated: state observations only). The device is the parameters'. Duck-typed, like :meth:`DeviceActor.from_sb3`."""
+        if not hasattr(critic, "q_networks"):
+            raise ValueError("not an SB3-shaped critic: no attribute 'q_networks'")
+        q_nets, kinds = [], set()
+        for net in critic.q_networks:
+            layers = []
+            for m in net:
+                if _is_linear(m):
+                    layers.append(m)
+                elif isinstance(m, torch.nn.ReLU):
+                    kinds.add("relu")
+                elif isinstance(m, torch.nn.Tanh):
+                    kinds.add("tanh")
+                else:
+                    raise ValueError(f"a q network holds a {type(m).__name__}: only Linear, ReLU and Tanh are built")
+            q_nets.append(layers)
+        if len(kinds) > 1:
+            raise ValueError("the q networks mix ReLU and Tanh")
+        if not q_nets or not q_nets[0]:
+            raise ValueError("q_networks holds no Linear layer")
+        if action_dim is None:
+            space = getattr(critic, "action_space", None)
+            if space is None or not getattr(space, "shape", None):
+                raise ValueError("the critic has no action_space.shape: give action_dim")
+            action_dim = int(space.shape[0])
+        first = q_nets[0][0]
+        return cls(first.weight.device, int(first.in_features) - int(action_dim), action_dim, q_nets, activation=kinds.pop() if kinds else "relu")
+
+    @staticmethod
+    def _as_nets(q_nets):
+        try:
+            nets = [list(net) for net in q_nets]
+        except TypeError:
+            raise ValueError("q_nets must be a list of 1..2 sequences of Linear layers (hidden..., out)") from None
+        if not 1 <= len(nets) <= nat.CRITIC_MAX_CRITICS:
+            raise ValueError(f"1..{nat.CRITIC_MAX_CRITICS} critics, got {len(nets)}")
+        for c, net in enumerate(nets):
+            if len(net) < 2:
+                raise ValueError(f"q_nets[{c}] needs at least one hidden layer and the output layer")
+            for m in net:
+                if not _is_linear(m):
+                    raise ValueError(f"{type(m).__name__} is not a Linear layer (weight, bias, in_features, out_features)")
+        return nets
+
+    def _check_modules(self, nets):
+        """Shapes, dtype and device of the modules' current parameters; ValueError before anything native sees them."""
+        if len(nets) != self.n_critics:
+            raise ValueError(f"this object holds {self.n_critics} critics, got {len(nets)}")
+        for c, net in enumerate(nets):
+            if len(net) != len(self.widths) + 1:
+                raise ValueError(f"q_nets[{c}] has {len(net) - 1} hidden layers, the critics of one object share an architecture ({len(self.widths)})")
+            fan_in = self.obs_dim + self.action_dim
+            for l, (m, width) in enumerate(zip(net, [*self.widths, 1])):
+                name = f"q_nets[{c}][{l}]"
+                if not 1 <= width <= nat.ACTOR_MAX_HIDDEN:
+                    raise ValueError(f"{name}: width {width} outside 1..{nat.ACTOR_MAX_HIDDEN}")
+                _check_parameters(name, m, "Linear", "critic", self.device)
+                if tuple(m.weight.shape) != (width, fan_in) or tuple(m.bias.shape) != (width,):
+                    raise ValueError(f"{name}: weight {tuple(m.weight.shape)} / bias {tuple(m.bias.shape)}, expected {(width, fan_in)} / {(width,)}")
+                fan_in = width
+
+    def _open(self):
+        if self._q is None:
+            raise nat.MjsError("the critic is closed")
+
+    def load(self, q_nets=None, tau=1.0):
+        """``packed = (1 - tau) * packed + tau * parameters`` for the CURRENT parameters of ``q_nets`` (default: the modules this object
+        was made from), ``tau`` in (0, 1]; ``tau = 1`` copies. Small kernels on the current stream, no synchronisation."""
+        self._open()
+        tau = float(tau)
+        if not 0.0 < tau <= 1.0:
+            raise ValueError(f"tau must lie in (0, 1], got {tau}")
+        if not self._loaded and tau != 1.0:
+            raise ValueError("a first load must have tau == 1: there is nothing to blend with yet")
+        nets = self.q_nets if q_nets is None else self._as_nets(q_nets)
+        self._check_modules(nets)
+        staged = [[(m.weight.detach().contiguous(), m.bias.detach().contiguous()) for m in net] for net in nets]
+        w = nat.MjsCriticWeights()
+        for c, net in enumerate(staged):
+            for l, (wt, bs) in enumerate(net[:-1]):
+                w.hidden_w[c][l], w.hidden_b[c][l] = wt.data_ptr(), bs.data_ptr()
+            w.out_w[c], w.out_b[c] = net[-1][0].data_ptr(), net[-1][1].data_ptr()
+        load = self._lib.mjs_critic_load
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        nat.check(load(self._q, C.byref(w), tau, C.c_void_p(stream)))
+        self._staged = staged  # alive until the next load: the pack kernels read them asynchronously
+        self._loaded = True
+
+    def q_values(self, obs, actions):
+        """float32 ``obs`` [B, obs_dim] and ``actions`` [B, action_dim] on the device -> float32 [n_critics, B], one launch on the current
+        stream; nothing is read back."""
+        from .replay import _want
+
+        self._open()
+        if not isinstance(obs, torch.Tensor) or obs.dim() != 2:
+            raise ValueError("obs must be a float32 tensor [B, obs_dim]")
+        B = int(obs.shape[0])
+        _want("obs", obs, (B, self.obs_dim), torch.float32, self.device)
+        _want("actions", actions, (B, self.action_dim), torch.float32, self.device)
+        q = torch.empty(self.n_critics, B, dtype=torch.float32, device=self.device)
+        if B:
+            launch = self._lib.mjs_critic_q
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            nat.check(launch(self._q, obs.data_ptr(), actions.data_ptr(), B, q.data_ptr(), C.c_void_p(stream)))
+        return q
+
+
+def sac_td_target(batch, actor, critic, gamma, ent_coef, z=None, generator=None, return_parts=False):
+    """The no-gradient half of SB3's ``SAC.train`` in ONE launch (csrc/mjs_critic.h)::
+
+        a', logp = actor.action_log_prob(next_obs);  target = r + (1 - done) * gamma * (min_c Q_c(next_obs, a') - ent_coef * logp)
+
+    ``batch``: what :meth:`DeviceReplayBuffer.sample` returns, or any dict with float32 ``next_obs`` [B, D], ``rewards`` [B] and ``dones``
+    [B] on the device; the batch's columns are the actor's inputs, in order. ``actor``: a state :class:`DeviceActor`, ``critic``: the
+    (target) :class:`DeviceCritic`, of the same widths D and A. ``ent_coef``: a float, or a one-element float32 device tensor (SB3's
+    learned coefficient, read by the kernel: no synchronisation). ``z``: float32 [B, A] standard-normal draws (default
+    ``torch.randn(B, A, generator=generator)`` on the device). Returns ``target`` float32 [B]; with ``return_parts`` a dict with
+    ``target``, ``next_actions`` [B, A], ``next_log_prob`` [B] and ``q_next`` [n_critics, B] (before the min). All argument checks raise
+    ``ValueError`` before any native call; nothing is read back."""
+    from .replay import _want
+
+    if not isinstance(actor, DeviceActor):
+        raise ValueError(f"actor must be a DeviceActor, got {type(actor).__name__}")
+    if not isinstance(critic, DeviceCritic):
+        raise ValueError(f"critic must be a DeviceCritic, got {type(critic).__name__}")
+    if actor.visual:
+        raise ValueError("a visual actor: visual critics are not built (state observations only)")
+    if actor.device != critic.device:
+        raise ValueError(f"the actor lives on {actor.device}, the critic on {critic.device}")
+    if actor.in_dim != critic.obs_dim:
+        raise ValueError(f"the actor reads {actor.in_dim} observation columns, the critic {critic.obs_dim}")
+    if actor.action_dim != critic.action_dim:
+        raise ValueError(f"the actor has {actor.action_dim} action components, the critic {critic.action_dim}")
+    gamma = float(gamma)
+    if not 0.0 <= gamma <= 1.0:
+        raise ValueError(f"gamma must lie in [0, 1], got {gamma}")
+    dev, D, A = critic.device, critic.obs_dim, critic.action_dim
+    if not isinstance(batch, dict) or any(k not in batch for k in ("next_obs", "rewards", "dones")):
+        raise ValueError("batch must be a dict with 'next_obs', 'rewards' and 'dones' (DeviceReplayBuffer.sample's result)")
+    next_obs = batch["next_obs"]
+    if not isinstance(next_obs, torch.Tensor) or next_obs.dim() != 2:
+        raise ValueError("batch['next_obs'] must be a float32 tensor [B, obs_dim]")
+    B = int(next_obs.shape[0])
+    if int(next_obs.shape[1]) != D:
+        raise ValueError(f"batch['next_obs'] has {int(next_obs.shape[1])} columns, the actor and the critic read {D}")
+    _want("batch['next_obs']", next_obs, (B, D), torch.float32, dev)
+    _want("batch['rewards']", batch["rewards"], (B,), torch.float32, dev)
+    _want("batch['dones']", batch["dones"], (B,), torch.float32, dev)
+    ent_dev = None
+    if isinstance(ent_coef, torch.Tensor):
+        ent_dev = _want("ent_coef", ent_coef, tuple(ent_coef.shape) if ent_coef.numel() == 1 and ent_coef.dim() <= 1 else (1,), torch.float32, dev)
+        ent_coef = 0.0
+    else:
+        try:
+            ent_coef = float(ent_coef)
+        except (TypeError, ValueError):
+            raise ValueError(f"ent_coef must be a float or a one-element float32 tensor, got {type(ent_coef).__name__}") from None
+    if z is not None:
+        _want("z", z, (B, A), torch.float32, dev)
+    if actor._a is None:
+        raise nat.MjsError("the actor is closed")
+    critic._open()
+    if z is None:
+        z = torch.randn(B, A, dtype=torch.float32, device=dev, generator=generator)
+    out = {"target": torch.empty(B, dtype=torch.float32, device=dev)}
+    if return_parts:
+        out.update(next_actions=torch.empty(B, A, dtype=torch.float32, device=dev), next_log_prob=torch.empty(B, dtype=torch.float32, device=dev),
+                   q_next=torch.empty(critic.n_critics, B, dtype=torch.float32, device=dev))
+    if B:
+        args = nat.MjsTdTargetArgs(B=B, next_obs_dev=next_obs.data_ptr(), rewards_dev=batch["rewards"].data_ptr(), dones_dev=batch["dones"].data_ptr(),
+                                   z_dev=z.data_ptr(), gamma=gamma, ent_coef=ent_coef, ent_coef_dev=ent_dev.data_ptr() if ent_dev is not None else None,
+                                   target_out_dev=out["target"].data_ptr(),
+                                   next_actions_out_dev=out["next_actions"].data_ptr() if return_parts else None,
+                                   next_log_prob_out_dev=out["next_log_prob"].data_ptr() if return_parts else None,
+                                   q_next_out_dev=out["q_next"].data_ptr() if return_parts else None)
+        launch = critic._lib.mjs_sac_td_target
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        nat.check(launch(actor._a, critic._q, C.byref(args), C.c_void_p(stream)))
+    return out if return_parts else out["target"]
