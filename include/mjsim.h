@@ -575,6 +575,62 @@ typedef struct {
  * critic's obs_dim or action_dim. B == 0 does nothing and returns 0. */
 int mjs_sac_td_target(const mjs_actor* actor, const mjs_critic* critic, const mjs_td_target_args* args, void* stream);
 
+/* The critic update of SAC.train on the device (csrc/mjs_critic_train.h; entry points added after abi 3 as well): for a batch and the
+ * target y of mjs_sac_td_target,
+ *   critic_loss = 0.5 * sum_c mean((Q_c(obs, actions) - y)^2);  zero_grad, backward, torch.optim.Adam.step  (amsgrad, weight decay: off)
+ * on the critic's PACKED copy, which becomes the master copy of the parameters: mjs_critic_q and mjs_sac_td_target see every step at
+ * once, a target critic blends from the online critic's packed copy (mjs_critic_blend), and mjs_critic_export writes torch.nn.Linear
+ * tensors when somebody wants them. float32 with float32 accumulation. The sum over the batch is bitwise reproducible: workgroups own
+ * contiguous 16-row tiles, store one partial slab each, and the slabs are summed in order (no atomics). */
+typedef struct mjs_critic_opt mjs_critic_opt;
+typedef struct {
+  uint32_t struct_size;      /* sizeof(mjs_critic_opt_desc) */
+  int32_t reserved0;         /* 0 */
+  double lr;                 /* >= 0: the default of mjs_critic_update's lr argument is the caller's business; kept for reference */
+  double beta1;              /* [0, 1) */
+  double beta2;              /* [0, 1) */
+  double eps;                /* > 0 */
+} mjs_critic_opt_desc;       /* 40 bytes */
+/* An optimiser is bound to ONE loaded critic, which must outlive it. It owns zeroed first and second moments, the slab workspace (the
+ * largest mjs_critic_train_workspace_bytes of any B) and the step count t = 0. MJS_ERR_INVALID_ARG for a null pointer, a wrong
+ * struct_size, a critic that was never loaded, lr < 0, a beta outside [0, 1) or eps <= 0. */
+int mjs_critic_opt_create(mjs_critic* critic, const mjs_critic_opt_desc* desc, mjs_critic_opt** out);
+void mjs_critic_opt_destroy(mjs_critic_opt* opt);
+/* Bytes of partial slabs a batch of B rows uses: splits(B) * n_critics * slab bytes, with tiles = ceil(B / 16), splits_max = min(128,
+ * max(1, 128 MiB / (n_critics * slab bytes))), tiles_per_split = ceil(tiles / splits_max), splits = ceil(tiles / tiles_per_split):
+ * a function of B and the shape alone. 0 for a null critic or B <= 0. */
+uint64_t mjs_critic_train_workspace_bytes(const mjs_critic* critic, int32_t B);
+typedef struct {
+  uint32_t struct_size;                  /* sizeof(mjs_critic_grad_args) */
+  int32_t B;                             /* batch rows: >= 0 */
+  const float* obs_dev;                  /* [B, obs_dim], required */
+  const float* actions_dev;              /* [B, action_dim], required */
+  const float* target_dev;               /* [B], required: y */
+  float* q_out_dev;                      /* [n_critics, B] or NULL: Q_c(obs, actions), mjs_critic_q's values bit for bit */
+  float* loss_out_dev;                   /* [n_critics] or NULL: mean((Q_c - y)^2) */
+  const mjs_critic_weights* grads_out;   /* HOST struct of DEVICE pointers the gradients are WRITTEN to, torch.nn.Linear layout, or NULL
+                                          * (mjs_critic_grad only; every layer of every critic < n_critics must be given) */
+} mjs_critic_grad_args;                  /* 56 bytes */
+/* The gradient of critic_loss with respect to every weight and bias, and no update: t and the parameters stay. One launch, and two small
+ * ones per layer where grads_out is given. MJS_ERR_INVALID_ARG (nothing launched, text in mjs_last_error(NULL)) for a null argument or
+ * required pointer, a wrong struct_size, B < 0, a critic that was never loaded, or an optimiser of another critic. B == 0 does nothing. */
+int mjs_critic_grad(const mjs_critic* critic, mjs_critic_opt* opt, const mjs_critic_grad_args* args, void* stream);
+/* One gradient step of the optimiser's critic: the gradient launch, then Adam over the packed copy (two launches), t += 1. lr >= 0 is
+ * given per call (SB3 evaluates its schedule per train()). With g the gradient, in float32, one rounding per operation:
+ *   m = m + (1 - beta1) * (g - m);  v = beta2 * v + (1 - beta2) * (g * g);  p = p - step_size * (m / (sqrtf(v) / sqrt_bc2 + eps))
+ * with (1 - beta1), beta2, (1 - beta2), sqrt_bc2 = sqrt(1 - beta2^t), eps and step_size = lr / (1 - beta1^t) computed in double on the
+ * host from the new t and rounded to float32 once each. Nothing is read back. Refusals as mjs_critic_grad's, and lr < 0 or a non-NULL
+ * grads_out. B == 0 does nothing (t stays). */
+int mjs_critic_update(mjs_critic_opt* opt, const mjs_critic_grad_args* args, double lr, void* stream);
+/* dst = (1 - tau) * dst + tau * src between the packed copies of two critics (polyak_update without torch modules), one launch, as
+ * fmaf(tau, src, (1 - tau) * dst) with both coefficients rounded to float32 on the host; tau == 1 copies and does not read dst.
+ * MJS_ERR_INVALID_ARG for a null critic, critics of different shapes or devices, a src that was never loaded, tau outside (0, 1], or
+ * tau != 1 into a dst that was never loaded. */
+int mjs_critic_blend(mjs_critic* dst_critic, const mjs_critic* src_critic, double tau, void* stream);
+/* The packed copy back into torch.nn.Linear layout: weights_out holds DEVICE pointers that are WRITTEN (every layer of every critic <
+ * n_critics). One small launch per layer. MJS_ERR_INVALID_ARG for a null pointer, a wrong struct_size or a critic never loaded. */
+int mjs_critic_export(const mjs_critic* critic, const mjs_critic_weights* weights_out, void* stream);
+
 /* Replaces the Robot entity's control API on a stand-alone UR5e (entities/robots/robot.py:198-272): Robot.moveJ :211-216,
  * Robot.movej_IK :198-209, Robot.servoL :218-225, Robot.servoJ :227-259, then n_substeps x (Robot.before_substep :261-272 +
  * JointTrajectory.get_target_joint_positions joint_trajectory.py:41-47; Physics.step), then Robot.get_tcp_pose :153-168.

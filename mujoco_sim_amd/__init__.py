@@ -18,7 +18,7 @@ from .environments.tasks.point_reach import PointMassReachTask
 from .environments.tasks.robot_reach import RobotReachConfig, RobotReachTask
 from .environments.tasks.robot_push_button import RobotPushButtonTask
 from .environments.tasks.robot_planar_push import RobotPushConfig, RobotPushTask
-from .policies import DeviceActor, DeviceCritic, DeviceEncoder, sac_td_target  # noqa: F401
+from .policies import DeviceActor, DeviceCritic, DeviceCriticOptimizer, DeviceEncoder, sac_td_target  # noqa: F401
 from .recording import LeRobotDatasetRecorder  # noqa: F401
 from .replay import DeviceReplayBuffer  # noqa: F401
 from .vector_env import TASKS, HipVectorEnv  # noqa: F401

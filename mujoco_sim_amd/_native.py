@@ -52,6 +52,8 @@ EXPORTED_SYMBOLS = [
     "mjs_actor_create_visual", "mjs_actor_actions_visual", "mjs_rollout_visual_actor",
     "mjs_replay_workspace_bytes", "mjs_replay_add", "mjs_replay_sample",
     "mjs_critic_create", "mjs_critic_destroy", "mjs_critic_load", "mjs_critic_q", "mjs_sac_td_target",
+    "mjs_critic_opt_create", "mjs_critic_opt_destroy", "mjs_critic_train_workspace_bytes", "mjs_critic_grad", "mjs_critic_update", "mjs_critic_blend",
+    "mjs_critic_export",
 ]
 
 
@@ -193,6 +195,17 @@ class MjsTdTargetArgs(_Sized):
                 ("next_actions_out_dev", C.c_void_p), ("next_log_prob_out_dev", C.c_void_p), ("q_next_out_dev", C.c_void_p)]
 
 
+class MjsCriticOptDesc(_Sized):
+    """mjs_critic_opt_desc: Adam's settings for a critic's packed copy."""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved0", C.c_int32), ("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double)]
+
+
+class MjsCriticGradArgs(_Sized):
+    """mjs_critic_grad_args: a batch's DEVICE tensors, the target, and where mjs_critic_grad / mjs_critic_update write."""
+    _fields_ = [("struct_size", C.c_uint32), ("B", C.c_int32), ("obs_dev", C.c_void_p), ("actions_dev", C.c_void_p), ("target_dev", C.c_void_p),
+                ("q_out_dev", C.c_void_p), ("loss_out_dev", C.c_void_p), ("grads_out", C.POINTER(MjsCriticWeights))]
+
+
 class MjsError(RuntimeError):
     pass
 
@@ -330,6 +343,15 @@ def lib() -> C.CDLL:
     L.mjs_critic_load.argtypes = [C.c_void_p, C.POINTER(MjsCriticWeights), C.c_double, C.c_void_p]
     L.mjs_critic_q.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
     L.mjs_sac_td_target.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(MjsTdTargetArgs), C.c_void_p]
+    L.mjs_critic_opt_create.argtypes = [C.c_void_p, C.POINTER(MjsCriticOptDesc), C.POINTER(C.c_void_p)]
+    L.mjs_critic_opt_destroy.argtypes = [C.c_void_p]
+    L.mjs_critic_opt_destroy.restype = None
+    L.mjs_critic_train_workspace_bytes.argtypes = [C.c_void_p, C.c_int32]
+    L.mjs_critic_train_workspace_bytes.restype = C.c_uint64
+    L.mjs_critic_grad.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(MjsCriticGradArgs), C.c_void_p]
+    L.mjs_critic_update.argtypes = [C.c_void_p, C.POINTER(MjsCriticGradArgs), C.c_double, C.c_void_p]
+    L.mjs_critic_blend.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_void_p]
+    L.mjs_critic_export.argtypes = [C.c_void_p, C.POINTER(MjsCriticWeights), C.c_void_p]
     L.mjs_get_rng_state.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.mjs_set_rng_state.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = L

@@ -22,6 +22,7 @@
 #include "mjs_encoder.h"
 #include "mjs_replay.h"
 #include "mjs_critic.h"
+#include "mjs_critic_train.h"
 #ifdef MJS_STAMPS
 #include "mjs_stamps_report.h"
 #endif
@@ -149,6 +150,19 @@ struct mjs_critic {
   float* w[crit::MAX_CRITICS][4] = {};  // packed [k][out] per critic: hidden layers, then (slot 3) the scalar head padded to act::OPAD
   float* b[crit::MAX_CRITICS][4] = {};
   bool loaded = false;               // mjs_critic_load has run
+};
+
+// Adam on one critic's packed copy (mjs_critic_train.h): the moments, the slab workspace and the step count.
+struct mjs_critic_opt {
+  mjs_critic* critic = nullptr;  // the critic it was created for; must outlive the optimiser
+  mjs_critic_opt_desc desc;
+  crit::Layout L;
+  int max_splits = 0;            // slabs the workspace holds per critic
+  float* m = nullptr;            // [n_critics][L.total], slab layout
+  float* v = nullptr;
+  float* slabs = nullptr;        // [max_splits][n_critics][L.total]
+  float* gsum = nullptr;         // [n_critics][L.total]: the summed gradient on its way to nn.Linear layout
+  int64_t t = 0;                 // optimiser steps taken
 };
 
 // An image encoder (mjs_encoder.h): the geometry, and the library's packed copy of the parameters. No per-handle state.
@@ -1401,6 +1415,235 @@ int mjs_sac_td_target(const mjs_actor* actor, const mjs_critic* q, const mjs_td_
   p.gamma = (float)args->gamma; p.ent_coef = (float)args->ent_coef; p.ent_coef_dev = args->ent_coef_dev;
   p.target = args->target_out_dev; p.next_actions = args->next_actions_out_dev; p.next_log_prob = args->next_log_prob_out_dev; p.q_next = args->q_next_out_dev;
   crit::td_target_kernel<<<dim3((unsigned)(((int64_t)args->B + crit::ROWS - 1) / crit::ROWS)), act::WAVES * 64, crit::lds_bytes(widest), (hipStream_t)stream>>>(p);
+  HIP_TRY(nullptr, hipGetLastError());
+  return MJS_OK;
+}
+
+// ---- the critic update (mjs_critic_train.h) -----------------------------------------------------------------------------------
+// where a critic's layers sit in a slab, and its packed copy as the segments' pointers
+static crit::Layout layout_of(const mjs_critic* q) {
+  crit::Layout L{};
+  int at = 0, K = q->k0;
+  for (int l = 0; l < 4; l++) {
+    const bool used = l < q->desc.n_hidden || l == 3;
+    const int O = l == 3 ? act::OPAD : q->width[l];
+    L.off[2 * l] = at;
+    if (used) at += K * O;
+    L.off[2 * l + 1] = at;
+    if (used) at += O;
+    if (used && l < 3) K = O;
+  }
+  L.off[8] = at;
+  L.total = at + 4;
+  return L;
+}
+static crit::Packed packed_of(const mjs_critic* q, int c) {
+  crit::Packed P;
+  for (int l = 0; l < 4; l++) { P.seg[2 * l] = q->w[c][l]; P.seg[2 * l + 1] = q->b[c][l]; }
+  return P;
+}
+static bool same_shape(const mjs_critic* a, const mjs_critic* b) {
+  bool same = a->desc.obs_dim == b->desc.obs_dim && a->desc.action_dim == b->desc.action_dim && a->desc.n_critics == b->desc.n_critics &&
+              a->desc.n_hidden == b->desc.n_hidden && a->desc.activation == b->desc.activation;
+  for (int l = 0; same && l < a->desc.n_hidden; l++) same = a->desc.hidden[l] == b->desc.hidden[l];
+  return same;
+}
+// every layer of every critic given? (mjs_critic_weights as inputs or as outputs)
+static bool all_layers_given(const mjs_critic* q, const mjs_critic_weights* w) {
+  for (int c = 0; c < q->desc.n_critics; c++) {
+    for (int l = 0; l < q->desc.n_hidden; l++)
+      if (!w->hidden_w[c][l] || !w->hidden_b[c][l]) return false;
+    if (!w->out_w[c] || !w->out_b[c]) return false;
+  }
+  return true;
+}
+// packed layers (w[c][slot], b[c][slot] of one critic's segments) -> nn.Linear layout, one launch per layer
+static void launch_unpack(const mjs_critic* q, const float* const* seg, int c, const mjs_critic_weights* out, hipStream_t s) {
+  int in = q->desc.obs_dim + q->desc.action_dim, K = q->k0;
+  for (int l = 0; l <= q->desc.n_hidden; l++) {
+    const bool head = l == q->desc.n_hidden;
+    const int slot = head ? 3 : l;
+    crit::UnpackParams p;
+    p.src_w = seg[2 * slot]; p.src_b = seg[2 * slot + 1];
+    p.K = K; p.O = head ? act::OPAD : q->width[l];
+    p.in = in; p.out = head ? 1 : q->desc.hidden[l];
+    p.dst_w = const_cast<float*>(head ? out->out_w[c] : out->hidden_w[c][l]);
+    p.dst_b = const_cast<float*>(head ? out->out_b[c] : out->hidden_b[c][l]);
+    crit::unpack_kernel<<<dim3((unsigned)((p.out * p.in + 255) / 256)), 256, 0, s>>>(p);
+    if (!head) { in = q->desc.hidden[l]; K = q->width[l]; }
+  }
+}
+
+int mjs_critic_opt_create(mjs_critic* q, const mjs_critic_opt_desc* desc, mjs_critic_opt** out) {
+  const std::string name = "mjs_critic_opt_create";
+  const auto refuse = [&](const std::string& why) { return fail(nullptr, MJS_ERR_INVALID_ARG, name + ": " + why); };
+  if (out) *out = nullptr;
+  if (!q || !desc || !out) return refuse("null argument");
+  if (desc->struct_size != sizeof(mjs_critic_opt_desc)) return refuse("mjs_critic_opt_desc.struct_size does not match this library's header");
+  if (!q->loaded) return refuse("the critic has no parameters yet (mjs_critic_load)");
+  if (!(desc->lr >= 0.0) || !std::isfinite(desc->lr)) return refuse("lr must be finite and >= 0");
+  if (!(desc->beta1 >= 0.0 && desc->beta1 < 1.0) || !(desc->beta2 >= 0.0 && desc->beta2 < 1.0)) return refuse("beta1 and beta2 must lie in [0, 1)");
+  if (!(desc->eps > 0.0) || !std::isfinite(desc->eps)) return refuse("eps must be finite and > 0");
+  DeviceGuard dev_(q->desc.device);
+  std::unique_ptr<mjs_critic_opt, void (*)(mjs_critic_opt*)> guard(new (std::nothrow) mjs_critic_opt(), mjs_critic_opt_destroy);
+  mjs_critic_opt* o = guard.get();
+  if (!o) return fail(nullptr, MJS_ERR_ALLOC, name + ": out of host memory");
+  CREATE_TRY(name, dev_.err);
+  o->critic = q;
+  o->desc = *desc;
+  o->L = layout_of(q);
+  const int nc = q->desc.n_critics;
+  o->max_splits = crit::splits_max(nc, o->L.total);
+  const size_t per = sizeof(float) * (size_t)nc * o->L.total;
+  CREATE_TRY(name, hipMalloc(&o->m, per));
+  CREATE_TRY(name, hipMalloc(&o->v, per));
+  CREATE_TRY(name, hipMalloc(&o->gsum, per));
+  CREATE_TRY(name, hipMalloc(&o->slabs, per * o->max_splits));
+  CREATE_TRY(name, hipMemset(o->m, 0, per));
+  CREATE_TRY(name, hipMemset(o->v, 0, per));
+  CREATE_TRY(name, hipDeviceSynchronize());  // the moments are zero before any stream's first step
+  // X, three hidden images and the gradient pair of the widest critic pass 64 KB: an opt-in, below the CU's 160 KB
+  static_assert(crit::train_lds_bytes(act::MAX_LAYERS, act::MAX_HIDDEN) <= 160 * 1024, "LDS images of grad_kernel");
+  CREATE_TRY(name, hipFuncSetAttribute(reinterpret_cast<const void*>(&crit::grad_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       (int)crit::train_lds_bytes(act::MAX_LAYERS, act::MAX_HIDDEN)));
+  *out = guard.release();
+  return MJS_OK;
+}
+
+void mjs_critic_opt_destroy(mjs_critic_opt* o) {
+  if (!o) return;
+  free_all({o->m, o->v, o->slabs, o->gsum});
+  delete o;
+}
+
+uint64_t mjs_critic_train_workspace_bytes(const mjs_critic* q, int32_t B) {
+  if (!q || B <= 0) return 0;
+  const crit::Layout L = layout_of(q);
+  return (uint64_t)crit::split_rule(B, q->desc.n_critics, L.total).splits * q->desc.n_critics * L.total * sizeof(float);
+}
+
+// what mjs_critic_grad and mjs_critic_update refuse alike; "" = fine
+static std::string grad_refusal(const mjs_critic* q, const mjs_critic_opt* o, const mjs_critic_grad_args* args) {
+  if (!q || !o || !args) return "critic, optimiser or args is null";
+  if (args->struct_size != sizeof(mjs_critic_grad_args)) return "mjs_critic_grad_args.struct_size does not match this library's header";
+  if (o->critic != q) return "the optimiser was created for another critic";
+  if (!q->loaded) return "the critic has no parameters yet (mjs_critic_load)";
+  if (args->B < 0) return "B is negative";
+  if (args->B > 0 && (!args->obs_dev || !args->actions_dev || !args->target_dev)) return "obs_dev, actions_dev or target_dev is null";
+  return "";
+}
+// the gradient launch into the optimiser's slabs; returns the splits it wrote
+static int launch_grad(const mjs_critic* q, mjs_critic_opt* o, const mjs_critic_grad_args* args, hipStream_t s) {
+  const crit::Split sp = crit::split_rule(args->B, q->desc.n_critics, o->L.total);
+  crit::GradParams p{};
+  p.c = critic_params(q, args->B, q->widest);
+  p.L = o->L;
+  p.tiles_per_split = sp.tiles_per_split;
+  p.inv_B = (float)(1.0 / (double)args->B);
+  p.obs = args->obs_dev; p.actions = args->actions_dev; p.target = args->target_dev;
+  p.q = args->q_out_dev;
+  p.slabs = o->slabs;
+  crit::grad_kernel<<<dim3((unsigned)sp.splits, (unsigned)q->desc.n_critics), act::WAVES * 64, crit::train_lds_bytes(q->desc.n_hidden, q->widest), s>>>(p);
+  return sp.splits;
+}
+static crit::SumParams sum_params(const mjs_critic* q, const mjs_critic_opt* o, const mjs_critic_grad_args* args, int splits) {
+  crit::SumParams p{};
+  p.L = o->L; p.n_critics = q->desc.n_critics; p.splits = splits;
+  p.inv_B = (float)(1.0 / (double)args->B);
+  p.slabs = o->slabs; p.loss = args->loss_out_dev;
+  return p;
+}
+
+int mjs_critic_grad(const mjs_critic* q, mjs_critic_opt* o, const mjs_critic_grad_args* args, void* stream) {
+  const auto refuse = [](const std::string& why) { return fail(nullptr, MJS_ERR_INVALID_ARG, "mjs_critic_grad: " + why); };
+  const std::string why = grad_refusal(q, o, args);
+  if (!why.empty()) return refuse(why);
+  if (args->grads_out) {
+    if (args->grads_out->struct_size != sizeof(mjs_critic_weights)) return refuse("mjs_critic_weights.struct_size does not match this library's header");
+    if (!all_layers_given(q, args->grads_out)) return refuse("grads_out: a layer's weight or bias pointer is null");
+  }
+  if (args->B == 0) return MJS_OK;
+  DeviceGuard dev_(q->desc.device);
+  HIP_TRY(nullptr, dev_.err);
+  const hipStream_t s = (hipStream_t)stream;
+  const int splits = launch_grad(q, o, args, s);
+  if (args->loss_out_dev || args->grads_out) {
+    const dim3 grid((unsigned)((o->L.off[8] + 1 + 255) / 256), (unsigned)q->desc.n_critics);
+    crit::slab_sum_kernel<<<grid, 256, 0, s>>>(sum_params(q, o, args, splits), o->gsum);
+  }
+  if (args->grads_out)
+    for (int c = 0; c < q->desc.n_critics; c++) {
+      const float* seg[8];
+      for (int k = 0; k < 8; k++) seg[k] = o->gsum + (size_t)c * o->L.total + o->L.off[k];
+      launch_unpack(q, seg, c, args->grads_out, s);
+    }
+  HIP_TRY(nullptr, hipGetLastError());
+  return MJS_OK;
+}
+
+int mjs_critic_update(mjs_critic_opt* o, const mjs_critic_grad_args* args, double lr, void* stream) {
+  const auto refuse = [](const std::string& why) { return fail(nullptr, MJS_ERR_INVALID_ARG, "mjs_critic_update: " + why); };
+  const std::string why = grad_refusal(o ? o->critic : nullptr, o, args);
+  if (!why.empty()) return refuse(why);
+  if (!(lr >= 0.0) || !std::isfinite(lr)) return refuse("lr must be finite and >= 0");
+  if (args->grads_out) return refuse("grads_out must be null (mjs_critic_grad returns gradients)");
+  if (args->B == 0) return MJS_OK;
+  mjs_critic* q = o->critic;
+  DeviceGuard dev_(q->desc.device);
+  HIP_TRY(nullptr, dev_.err);
+  const hipStream_t s = (hipStream_t)stream;
+  const int splits = launch_grad(q, o, args, s);
+  const double t = (double)(o->t + 1);
+  crit::AdamParams p{};
+  p.s = sum_params(q, o, args, splits);
+  for (int c = 0; c < q->desc.n_critics; c++) p.net[c] = packed_of(q, c);
+  p.m = o->m; p.v = o->v;
+  p.one_minus_beta1 = (float)(1.0 - o->desc.beta1);
+  p.beta2 = (float)o->desc.beta2;
+  p.one_minus_beta2 = (float)(1.0 - o->desc.beta2);
+  p.sqrt_bc2 = (float)std::sqrt(1.0 - std::pow(o->desc.beta2, t));
+  p.eps = (float)o->desc.eps;
+  p.step_size = (float)(lr / (1.0 - std::pow(o->desc.beta1, t)));
+  crit::adam_kernel<<<dim3((unsigned)((o->L.off[8] + 1 + 255) / 256), (unsigned)q->desc.n_critics), 256, 0, s>>>(p);
+  HIP_TRY(nullptr, hipGetLastError());
+  o->t += 1;
+  return MJS_OK;
+}
+
+int mjs_critic_blend(mjs_critic* dst, const mjs_critic* src, double tau, void* stream) {
+  const auto refuse = [](const std::string& why) { return fail(nullptr, MJS_ERR_INVALID_ARG, "mjs_critic_blend: " + why); };
+  if (!dst || !src) return refuse("null critic");
+  if (!same_shape(dst, src)) return refuse("the two critics differ in shape");
+  if (dst->desc.device != src->desc.device) return refuse("the two critics live on different devices");
+  if (!src->loaded) return refuse("the source critic has no parameters yet (mjs_critic_load)");
+  if (!(tau > 0.0 && tau <= 1.0)) return refuse("tau must lie in (0, 1]");
+  if (!dst->loaded && tau != 1.0) return refuse("a critic that was never loaded takes tau == 1 only (there is nothing to blend with yet)");
+  if (dst == src) return MJS_OK;  // a blend of a copy with itself
+  DeviceGuard dev_(dst->desc.device);
+  HIP_TRY(nullptr, dev_.err);
+  crit::BlendParams p{};
+  p.L = layout_of(dst);
+  for (int c = 0; c < dst->desc.n_critics; c++) { p.dst[c] = packed_of(dst, c); p.src[c] = packed_of(src, c); }
+  const dim3 grid((unsigned)((p.L.off[8] + 255) / 256), (unsigned)dst->desc.n_critics);
+  if (tau == 1.0) crit::blend_kernel<true><<<grid, 256, 0, (hipStream_t)stream>>>(p, 0.0f, 1.0f);
+  else crit::blend_kernel<false><<<grid, 256, 0, (hipStream_t)stream>>>(p, (float)(1.0 - tau), (float)tau);
+  HIP_TRY(nullptr, hipGetLastError());
+  dst->loaded = true;
+  return MJS_OK;
+}
+
+int mjs_critic_export(const mjs_critic* q, const mjs_critic_weights* out, void* stream) {
+  const auto refuse = [](const std::string& why) { return fail(nullptr, MJS_ERR_INVALID_ARG, "mjs_critic_export: " + why); };
+  if (!q || !out) return refuse("null argument");
+  if (out->struct_size != sizeof(mjs_critic_weights)) return refuse("mjs_critic_weights.struct_size does not match this library's header");
+  if (!q->loaded) return refuse("the critic has no parameters yet (mjs_critic_load)");
+  if (!all_layers_given(q, out)) return refuse("a layer's weight or bias pointer is null");
+  DeviceGuard dev_(q->desc.device);
+  HIP_TRY(nullptr, dev_.err);
+  for (int c = 0; c < q->desc.n_critics; c++) {
+    const crit::Packed P = packed_of(q, c);
+    launch_unpack(q, P.seg, c, out, (hipStream_t)stream);
+  }
   HIP_TRY(nullptr, hipGetLastError());
   return MJS_OK;
 }

@@ -436,8 +436,10 @@ class DeviceActor(_NativeObject):
 
 class DeviceCritic(_NativeObject):
     """SAC's critics (SB3's ``ContinuousCritic``: ``n_critics`` MLPs over ``[obs | action]`` with a scalar head) held by libmjsim.so
-    for one device (csrc/mjs_critic.h). Forward only: :meth:`q_values` and :func:`sac_td_target` take no gradient; the critic and
-    actor losses stay in torch. float32 with float32 accumulation, like :class:`DeviceActor`.
+    for one device (csrc/mjs_critic.h). :meth:`q_values` and :func:`sac_td_target` take no gradient; the critic loss, its gradients
+    and the Adam step run on the packed copy through :class:`DeviceCriticOptimizer` (csrc/mjs_critic_train.h), a target critic follows
+    with :meth:`blend_from`, and :meth:`export` writes the trained parameters back into torch modules for the actor loss, which stays
+    in torch. float32 with float32 accumulation, like :class:`DeviceActor`.
 
     The object keeps references to the torch modules it was made from; :meth:`load` packs their CURRENT parameters, or blends those
     of other modules of the same shapes into the packed copy (``tau < 1``: SB3's ``polyak_update``), so that a TARGET critic can
@@ -555,7 +557,10 @@ class DeviceCritic(_NativeObject):
 
     def load(self, q_nets=None, tau=1.0):
         """``packed = (1 - tau) * packed + tau * parameters`` for the CURRENT parameters of ``q_nets`` (default: the modules this object
-        was made from), ``tau`` in (0, 1]; ``tau = 1`` copies. Small kernels on the current stream, no synchronisation."""
+        was made from), ``tau`` in (0, 1]; ``tau = 1`` copies. Small kernels on the current stream, no synchronisation.
+
+        Once a :class:`DeviceCriticOptimizer` has stepped this critic, the packed copy is the master copy and the modules are stale:
+        ``load()`` with no argument would overwrite the trained parameters with them. :meth:`export` is the way back into torch."""
         self._open()
         tau = float(tau)
         if not 0.0 < tau <= 1.0:
@@ -593,6 +598,186 @@ class DeviceCritic(_NativeObject):
             stream = torch.cuda.current_stream(self.device).cuda_stream
             nat.check(launch(self._q, obs.data_ptr(), actions.data_ptr(), B, q.data_ptr(), C.c_void_p(stream)))
         return q
+
+    def _weights_struct(self, tensors):
+        """mjs_critic_weights over ``tensors[c][l] = (weight, bias)``."""
+        w = nat.MjsCriticWeights()
+        for c, net in enumerate(tensors):
+            for l, (wt, bs) in enumerate(net[:-1]):
+                w.hidden_w[c][l], w.hidden_b[c][l] = wt.data_ptr(), bs.data_ptr()
+            w.out_w[c], w.out_b[c] = net[-1][0].data_ptr(), net[-1][1].data_ptr()
+        return w
+
+    def _empty_like_parameters(self):
+        """Fresh contiguous float32 tensors in ``nn.Linear`` shapes: ``[c][l] = (weight, bias)``."""
+        out = []
+        for _ in range(self.n_critics):
+            net, fan_in = [], self.obs_dim + self.action_dim
+            for width in [*self.widths, 1]:
+                net.append((torch.empty(width, fan_in, dtype=torch.float32, device=self.device), torch.empty(width, dtype=torch.float32, device=self.device)))
+                fan_in = width
+            out.append(net)
+        return out
+
+    def export(self, q_nets=None):
+        """The packed parameters into the ``torch.nn.Linear`` modules ``q_nets`` (default: the modules this object was made from), with
+        ``copy_`` under ``no_grad``: after steps of a :class:`DeviceCriticOptimizer`, an actor loss that stays in torch sees the trained
+        critic. Small kernels on the current stream, no synchronisation. Returns the modules."""
+        self._open()
+        nets = self.q_nets if q_nets is None else self._as_nets(q_nets)
+        self._check_modules(nets)
+        staged = self._empty_like_parameters()
+        w = self._weights_struct(staged)
+        launch = self._lib.mjs_critic_export
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        nat.check(launch(self._q, C.byref(w), C.c_void_p(stream)))
+        with torch.no_grad():
+            for net, tensors in zip(nets, staged):
+                for m, (wt, bs) in zip(net, tensors):
+                    m.weight.copy_(wt)
+                    m.bias.copy_(bs)
+        return nets
+
+    def blend_from(self, other, tau):
+        """``packed = (1 - tau) * packed + tau * other's packed`` (SB3's ``polyak_update`` between two packed copies, one launch): what a
+        target critic does after every step of the online critic's optimiser. ``other``: a :class:`DeviceCritic` of the same shape on
+        the same device; ``tau`` in (0, 1], ``tau = 1`` copies."""
+        if not isinstance(other, DeviceCritic):
+            raise ValueError(f"other must be a DeviceCritic, got {type(other).__name__}")
+        tau = float(tau)
+        if not 0.0 < tau <= 1.0:
+            raise ValueError(f"tau must lie in (0, 1], got {tau}")
+        if other.device != self.device:
+            raise ValueError(f"the other critic lives on {other.device}, this one on {self.device}")
+        mine, theirs = (self.obs_dim, self.action_dim, self.n_critics, self.widths, self.activation), \
+                       (other.obs_dim, other.action_dim, other.n_critics, other.widths, other.activation)
+        if mine != theirs:
+            raise ValueError(f"the critics differ in shape: (obs_dim, action_dim, n_critics, widths, activation) {mine} against {theirs}")
+        if not self._loaded and tau != 1.0:
+            raise ValueError("a critic without parameters takes tau == 1 only: there is nothing to blend with yet")
+        self._open()
+        other._open()
+        blend = self._lib.mjs_critic_blend
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        nat.check(blend(self._q, other._q, tau, C.c_void_p(stream)))
+        self._loaded = True
+
+
+class DeviceCriticOptimizer(_NativeObject):
+    """The critic update of SB3's ``SAC.train`` on a :class:`DeviceCritic`'s packed parameters (csrc/mjs_critic_train.h)::
+
+        critic_loss = 0.5 * sum(F.mse_loss(q, target) for q in critic(obs, actions))
+        critic.optimizer.zero_grad(); critic_loss.backward(); critic.optimizer.step()        # torch.optim.Adam, SB3's defaults
+
+    as two launches per :meth:`step`: the forward and backward pass with a bitwise reproducible sum over the batch, then Adam. The
+    packed copy is the master copy from the first step on: ``critic.q_values`` and :func:`sac_td_target` see every step at once, a
+    target critic follows with ``target.blend_from(critic, tau)``, ``critic.export()`` refreshes the torch modules, and
+    ``critic.load()`` would overwrite the trained parameters with the stale modules. The optimiser keeps the critic alive."""
+    _handle, _destroy = "_o", "mjs_critic_opt_destroy"
+
+    def __init__(self, critic, lr=3e-4, betas=(0.9, 0.999), eps=1e-8):
+        self._o = None
+        if not isinstance(critic, DeviceCritic):
+            raise ValueError(f"critic must be a DeviceCritic, got {type(critic).__name__}")
+        self.lr = self._checked_lr(lr)
+        try:
+            beta1, beta2 = (float(b) for b in betas)
+        except (TypeError, ValueError):
+            raise ValueError("betas must be two floats in [0, 1)") from None
+        if not (0.0 <= beta1 < 1.0 and 0.0 <= beta2 < 1.0):
+            raise ValueError(f"betas must lie in [0, 1), got {(beta1, beta2)}")
+        eps = float(eps)
+        if not 0.0 < eps < float("inf"):
+            raise ValueError(f"eps must be positive and finite, got {eps}")
+        self.betas, self.eps = (beta1, beta2), eps
+        self.critic, self.device = critic, critic.device
+        self.step_count = 0
+        critic._open()
+        # ---- native from here on
+        self._lib = critic._lib
+        desc = nat.MjsCriticOptDesc(lr=self.lr, beta1=beta1, beta2=beta2, eps=eps)
+        o = C.c_void_p()
+        nat.check(self._lib.mjs_critic_opt_create(critic._q, C.byref(desc), C.byref(o)))
+        self._o = o
+
+    @staticmethod
+    def _checked_lr(lr):
+        try:
+            lr = float(lr)
+        except (TypeError, ValueError):
+            raise ValueError(f"lr must be a float, got {type(lr).__name__}") from None
+        if not 0.0 <= lr < float("inf"):
+            raise ValueError(f"lr must be finite and >= 0, got {lr}")
+        return lr
+
+    def _batch(self, batch, target):
+        """(obs, actions, target, B) checked; ValueError before anything native."""
+        from .replay import _want
+
+        c = self.critic
+        if not isinstance(batch, dict) or any(k not in batch for k in ("obs", "actions")):
+            raise ValueError("batch must be a dict with 'obs' and 'actions' (DeviceReplayBuffer.sample's result)")
+        obs = batch["obs"]
+        if not isinstance(obs, torch.Tensor) or obs.dim() != 2:
+            raise ValueError("batch['obs'] must be a float32 tensor [B, obs_dim]")
+        B = int(obs.shape[0])
+        _want("batch['obs']", obs, (B, c.obs_dim), torch.float32, self.device)
+        _want("batch['actions']", batch["actions"], (B, c.action_dim), torch.float32, self.device)
+        _want("target", target, (B,), torch.float32, self.device)
+        return obs, batch["actions"], target, B
+
+    def _open(self):
+        self.critic._open()
+        if self._o is None:
+            raise nat.MjsError("the optimiser is closed")
+
+    def _args(self, obs, actions, target, B, q, loss, grads=None):
+        return nat.MjsCriticGradArgs(B=B, obs_dev=obs.data_ptr(), actions_dev=actions.data_ptr(), target_dev=target.data_ptr(),
+                                     q_out_dev=q.data_ptr() if q is not None else None, loss_out_dev=loss.data_ptr() if loss is not None else None,
+                                     grads_out=C.pointer(grads) if grads is not None else None)
+
+    def step(self, batch, target, lr=None, return_parts=False):
+        """One gradient step on ``batch`` (:meth:`DeviceReplayBuffer.sample`'s dict: float32 ``obs`` [B, obs_dim] and ``actions``
+        [B, action_dim]) towards ``target`` float32 [B] (:func:`sac_td_target`), with the learning rate ``lr`` (default: the
+        constructor's; SB3 evaluates its schedule per ``train``). Two launches on the current stream; nothing is read back. Returns
+        ``None``, or with ``return_parts`` a dict with ``loss`` [n_critics] (``mean((q_c - target)^2)`` BEFORE the step) and ``q``
+        [n_critics, B]. An empty batch does nothing and is not counted."""
+        obs, actions, target, B = self._batch(batch, target)
+        lr = self.lr if lr is None else self._checked_lr(lr)
+        self._open()
+        c = self.critic
+        q = loss = None
+        if return_parts:
+            q = torch.empty(c.n_critics, B, dtype=torch.float32, device=self.device)
+            loss = torch.zeros(c.n_critics, dtype=torch.float32, device=self.device)
+        if B:
+            args = self._args(obs, actions, target, B, q, loss)
+            update = self._lib.mjs_critic_update
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            nat.check(update(self._o, C.byref(args), lr, C.c_void_p(stream)))
+            self.step_count += 1
+        return {"loss": loss, "q": q} if return_parts else None
+
+    def gradients(self, batch, target):
+        """The gradients :meth:`step` would apply, and no update: a dict with ``grads`` (per critic a list of ``(weight_grad,
+        bias_grad)`` in ``nn.Linear`` shapes, hidden layers then the head), ``q`` [n_critics, B] and ``loss`` [n_critics]."""
+        obs, actions, target, B = self._batch(batch, target)
+        self._open()
+        c = self.critic
+        q = torch.empty(c.n_critics, B, dtype=torch.float32, device=self.device)
+        loss = torch.zeros(c.n_critics, dtype=torch.float32, device=self.device)
+        grads = c._empty_like_parameters()
+        if B:
+            args = self._args(obs, actions, target, B, q, loss, c._weights_struct(grads))
+            grad = self._lib.mjs_critic_grad
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            nat.check(grad(c._q, self._o, C.byref(args), C.c_void_p(stream)))
+        else:
+            for net in grads:
+                for wt, bs in net:
+                    wt.zero_()
+                    bs.zero_()
+        return {"grads": grads, "q": q, "loss": loss}
 
 
 def sac_td_target(batch, actor, critic, gamma, ent_coef, z=None, generator=None, return_parts=False):
