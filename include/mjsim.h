@@ -631,6 +631,82 @@ int mjs_critic_blend(mjs_critic* dst_critic, const mjs_critic* src_critic, doubl
  * n_critics). One small launch per layer. MJS_ERR_INVALID_ARG for a null pointer, a wrong struct_size or a critic never loaded. */
 int mjs_critic_export(const mjs_critic* critic, const mjs_critic_weights* weights_out, void* stream);
 
+/* The actor and entropy-coefficient update of SAC.train on the device (csrc/mjs_actor_train.h; entry points added after abi 3 as well):
+ *   a, logp = actor.action_log_prob(obs)  on the caller's draws z, as mjs_sac_td_target computes a' and logp
+ *   actor_loss = mean(ent_coef * logp - min_c Q_c(obs, a));  zero_grad, backward, torch.optim.Adam.step on the ACTOR alone
+ *   ent_coef_loss = -mean(log_ent_coef * (logp + target_entropy));  Adam on log_ent_coef;  ent_coef = expf(log_ent_coef)   (optional)
+ * on the actor's PACKED copy, which becomes the master copy of the parameters: mjs_actor_actions, mjs_rollout_actor and
+ * mjs_sac_td_target see every step at once, and mjs_actor_export writes torch.nn.Linear tensors when somebody wants them. Both losses
+ * use the ent_coef from BEFORE this call's entropy step. The critics are read, never written; their parameter gradients are not computed.
+ * float32 with float32 accumulation; the sum over the batch is bitwise reproducible, by the scheme of mjs_critic_update. */
+typedef struct mjs_actor_opt mjs_actor_opt;
+typedef struct {
+  uint32_t struct_size;      /* sizeof(mjs_actor_opt_desc) */
+  int32_t reserved0;         /* 0 */
+  double lr;                 /* >= 0; kept for reference, mjs_actor_update takes lr per call */
+  double beta1;              /* [0, 1) */
+  double beta2;              /* [0, 1) */
+  double eps;                /* > 0 */
+} mjs_actor_opt_desc;        /* 40 bytes */
+/* An optimiser is bound to ONE loaded actor of mjs_actor_create, which must outlive it. It owns zeroed first and second moments, the slab
+ * workspace (the largest mjs_actor_train_workspace_bytes of any B) and the step count t = 0. MJS_ERR_INVALID_ARG for a null pointer, a
+ * wrong struct_size, an actor that was never loaded or reads feature blocks, lr < 0, a beta outside [0, 1) or eps <= 0. */
+int mjs_actor_opt_create(mjs_actor* actor, const mjs_actor_opt_desc* desc, mjs_actor_opt** out);
+void mjs_actor_opt_destroy(mjs_actor_opt* opt);
+/* Bytes of partial slabs a batch of B rows uses: mjs_critic_train_workspace_bytes' rule with n_critics = 1 over the actor's slab (every
+ * layer's packed weights and bias, the stacked head last, and 4 floats). 0 for a null or visual actor or B <= 0. */
+uint64_t mjs_actor_train_workspace_bytes(const mjs_actor* actor, int32_t B);
+/* SB3's learned entropy coefficient (ent_coef = "auto"): four DEVICE floats of the caller's and the HOST values of one Adam step. */
+typedef struct {
+  uint32_t struct_size;        /* sizeof(mjs_entropy_step) */
+  int32_t reserved0;           /* 0 */
+  float* log_ent_coef_dev;     /* one float, required: updated */
+  float* ent_coef_dev;         /* one float, required: WRITTEN expf(log_ent_coef) after the step */
+  float* m_dev;                /* one float, required: Adam's first moment */
+  float* v_dev;                /* one float, required: Adam's second moment */
+  int64_t t;                   /* >= 1: the scalar's step count AFTER this step */
+  double lr;                   /* >= 0 */
+  double beta1;                /* [0, 1) */
+  double beta2;                /* [0, 1) */
+  double eps;                  /* > 0 */
+  double target_entropy;       /* rounded to float32 */
+} mjs_entropy_step;            /* 88 bytes */
+typedef struct {
+  uint32_t struct_size;                  /* sizeof(mjs_actor_grad_args) */
+  int32_t B;                             /* batch rows: >= 0 */
+  const float* obs_dev;                  /* [B, obs_dim], required: the actor's input columns in order (its obs_index plays no role) */
+  const float* z_dev;                    /* [B, action_dim], required: standard-normal draws */
+  const mjs_critic* critic;              /* required: loaded, on the actor's device, obs_dim == in_dim, the same action_dim */
+  double ent_coef;                       /* rounded to float32; ignored where ent_coef_dev is given */
+  const float* ent_coef_dev;             /* one float32 on the device, read by the gradient launch, or NULL */
+  float* actions_out_dev;                /* [B, action_dim] or NULL: a */
+  float* log_prob_out_dev;               /* [B] or NULL: logp */
+  float* q_pi_out_dev;                   /* [n_critics, B] or NULL: Q_c(obs, a), mjs_critic_q's values bit for bit */
+  float* min_q_action_grad_out_dev;      /* [B, action_dim] or NULL: d(min_c Q_c)/da */
+  float* loss_out_dev;                   /* [1] or NULL: actor_loss */
+  const mjs_actor_weights* grads_out;    /* HOST struct of DEVICE pointers the gradients are WRITTEN to, torch.nn.Linear layout, or NULL
+                                          * (mjs_actor_grad only; every layer must be given) */
+  const mjs_entropy_step* entropy;       /* NULL, or the entropy step mjs_actor_update takes after the actor's (mjs_actor_grad checks it
+                                          * and uses its target_entropy only) */
+} mjs_actor_grad_args;                   /* 104 bytes */
+/* The gradient of actor_loss with respect to every weight and bias of the actor, and no update: t, the parameters and the entropy
+ * scalars stay. One launch, and two small ones per layer where grads_out is given. MJS_ERR_INVALID_ARG (nothing launched, text in
+ * mjs_last_error(NULL)) for a null argument or required pointer, a wrong struct_size, B < 0, an actor or critic that was never loaded,
+ * an actor of mjs_actor_create_visual, actor and critic of different devices, an actor whose in_dim or action_dim is not the critic's
+ * obs_dim or action_dim, an optimiser of another actor, or an entropy block with a null pointer, lr < 0, t < 1, a beta outside [0, 1)
+ * or eps <= 0. B == 0 does nothing. */
+int mjs_actor_grad(const mjs_actor* actor, mjs_actor_opt* opt, const mjs_actor_grad_args* args, void* stream);
+/* One gradient step of the optimiser's actor: the gradient launch, then Adam over the packed copy by the lines and the coefficient rule
+ * of mjs_critic_update (two launches), t += 1; with an entropy block a third, one-thread launch:
+ *   g = -(sum of (logp + target_entropy) in row order) * (1 / B);  the same Adam lines on log_ent_coef;  ent_coef = expf(log_ent_coef)
+ * with the block's own t, lr, betas and eps. The gradient launch has read ent_coef before that write, in stream order. Nothing is read
+ * back. Refusals as mjs_actor_grad's, and lr < 0 or a non-NULL grads_out. B == 0 does nothing (t stays). */
+int mjs_actor_update(mjs_actor_opt* opt, const mjs_actor_grad_args* args, double lr, void* stream);
+/* The packed copy back into torch.nn.Linear layout, the head unstacked into mu and log_std: weights_out holds DEVICE pointers that are
+ * WRITTEN (every layer). One small launch per layer and two for the head. MJS_ERR_INVALID_ARG for a null pointer, a wrong struct_size, a
+ * visual actor or an actor never loaded. */
+int mjs_actor_export(const mjs_actor* actor, const mjs_actor_weights* weights_out, void* stream);
+
 /* Replaces the Robot entity's control API on a stand-alone UR5e (entities/robots/robot.py:198-272): Robot.moveJ :211-216,
  * Robot.movej_IK :198-209, Robot.servoL :218-225, Robot.servoJ :227-259, then n_substeps x (Robot.before_substep :261-272 +
  * JointTrajectory.get_target_joint_positions joint_trajectory.py:41-47; Physics.step), then Robot.get_tcp_pose :153-168.

@@ -18,7 +18,8 @@ from .environments.tasks.point_reach import PointMassReachTask
 from .environments.tasks.robot_reach import RobotReachConfig, RobotReachTask
 from .environments.tasks.robot_push_button import RobotPushButtonTask
 from .environments.tasks.robot_planar_push import RobotPushConfig, RobotPushTask
-from .policies import DeviceActor, DeviceCritic, DeviceCriticOptimizer, DeviceEncoder, sac_td_target  # noqa: F401
+from .policies import (DeviceActor, DeviceActorOptimizer, DeviceCritic, DeviceCriticOptimizer, DeviceEncoder, DeviceEntropyCoef,  # noqa: F401
+                       sac_gradient_step, sac_td_target)
 from .recording import LeRobotDatasetRecorder  # noqa: F401
 from .replay import DeviceReplayBuffer  # noqa: F401
 from .vector_env import TASKS, HipVectorEnv  # noqa: F401

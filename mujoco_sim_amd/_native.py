@@ -54,6 +54,7 @@ EXPORTED_SYMBOLS = [
     "mjs_critic_create", "mjs_critic_destroy", "mjs_critic_load", "mjs_critic_q", "mjs_sac_td_target",
     "mjs_critic_opt_create", "mjs_critic_opt_destroy", "mjs_critic_train_workspace_bytes", "mjs_critic_grad", "mjs_critic_update", "mjs_critic_blend",
     "mjs_critic_export",
+    "mjs_actor_opt_create", "mjs_actor_opt_destroy", "mjs_actor_train_workspace_bytes", "mjs_actor_grad", "mjs_actor_update", "mjs_actor_export",
 ]
 
 
@@ -206,6 +207,26 @@ class MjsCriticGradArgs(_Sized):
                 ("q_out_dev", C.c_void_p), ("loss_out_dev", C.c_void_p), ("grads_out", C.POINTER(MjsCriticWeights))]
 
 
+class MjsActorOptDesc(_Sized):
+    """mjs_actor_opt_desc: Adam's settings for an actor's packed copy."""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved0", C.c_int32), ("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double)]
+
+
+class MjsEntropyStep(_Sized):
+    """mjs_entropy_step: SB3's learned entropy coefficient as DEVICE scalars, and the HOST values of its Adam step."""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved0", C.c_int32), ("log_ent_coef_dev", C.c_void_p), ("ent_coef_dev", C.c_void_p), ("m_dev", C.c_void_p),
+                ("v_dev", C.c_void_p), ("t", C.c_int64), ("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double),
+                ("target_entropy", C.c_double)]
+
+
+class MjsActorGradArgs(_Sized):
+    """mjs_actor_grad_args: a batch's DEVICE tensors, the critic, the entropy coefficient, and where mjs_actor_grad / mjs_actor_update write."""
+    _fields_ = [("struct_size", C.c_uint32), ("B", C.c_int32), ("obs_dev", C.c_void_p), ("z_dev", C.c_void_p), ("critic", C.c_void_p),
+                ("ent_coef", C.c_double), ("ent_coef_dev", C.c_void_p), ("actions_out_dev", C.c_void_p), ("log_prob_out_dev", C.c_void_p),
+                ("q_pi_out_dev", C.c_void_p), ("min_q_action_grad_out_dev", C.c_void_p), ("loss_out_dev", C.c_void_p),
+                ("grads_out", C.POINTER(MjsActorWeights)), ("entropy", C.POINTER(MjsEntropyStep))]
+
+
 class MjsError(RuntimeError):
     pass
 
@@ -352,6 +373,14 @@ def lib() -> C.CDLL:
     L.mjs_critic_update.argtypes = [C.c_void_p, C.POINTER(MjsCriticGradArgs), C.c_double, C.c_void_p]
     L.mjs_critic_blend.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_void_p]
     L.mjs_critic_export.argtypes = [C.c_void_p, C.POINTER(MjsCriticWeights), C.c_void_p]
+    L.mjs_actor_opt_create.argtypes = [C.c_void_p, C.POINTER(MjsActorOptDesc), C.POINTER(C.c_void_p)]
+    L.mjs_actor_opt_destroy.argtypes = [C.c_void_p]
+    L.mjs_actor_opt_destroy.restype = None
+    L.mjs_actor_train_workspace_bytes.argtypes = [C.c_void_p, C.c_int32]
+    L.mjs_actor_train_workspace_bytes.restype = C.c_uint64
+    L.mjs_actor_grad.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(MjsActorGradArgs), C.c_void_p]
+    L.mjs_actor_update.argtypes = [C.c_void_p, C.POINTER(MjsActorGradArgs), C.c_double, C.c_void_p]
+    L.mjs_actor_export.argtypes = [C.c_void_p, C.POINTER(MjsActorWeights), C.c_void_p]
     L.mjs_get_rng_state.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.mjs_set_rng_state.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = L

@@ -111,6 +111,25 @@ __global__ __launch_bounds__(act::WAVES * 64) void q_kernel(CriticParams p, cons
   });
 }
 
+// One component of SB3's actor.action_log_prob for the clamped log_std ls and the draw zj: returns a = tanhf(mu + expf(ls) zj), and the
+// component's two log-probability terms. What td_target_kernel and atrain::grad_kernel (mjs_actor_train.h) share, so that both give the
+// same bits.
+__device__ __forceinline__ float squashed_sample(float mu, float ls, float zj, float& gauss, float& corr) {
+  const float a = tanhf(mu + expf(ls) * zj);
+  {
+    // Normal(mu, exp(ls)).log_prob(u) at u = mu + exp(ls) z, and the squash correction, operation by operation
+#pragma clang fp contract(off)
+    const float zz = zj * zj;
+    const float h = -0.5f * zz;
+    const float hl = h - ls;
+    gauss = hl - HALF_LOG_2PI;
+    const float aa = a * a;
+    const float one = 1.0f - aa;
+    corr = logf(one + LOG_PROB_EPS);
+  }
+  return a;
+}
+
 struct TdParams {
   CriticParams c;
   Mlp actor;                    // k0 = D padded to KPAD (<= the critics' k0); its head: mu in columns 0..A-1, log_std in A..2A-1
@@ -149,19 +168,8 @@ __global__ __launch_bounds__(act::WAVES * 64) void td_target_kernel(TdParams p) 
       const float mu = head[r * S + j];
       const float ls = fminf(fmaxf(head[r * S + A + j], act::LOG_STD_MIN), act::LOG_STD_MAX);
       const float zj = p.z[(size_t)i * A + j];
-      a = tanhf(mu + expf(ls) * zj);
+      a = squashed_sample(mu, ls, zj, gauss, corr);
       if (p.next_actions) p.next_actions[(size_t)i * A + j] = a;
-      {
-        // Normal(mu, exp(ls)).log_prob(u) at u = mu + exp(ls) z, and the squash correction, operation by operation
-#pragma clang fp contract(off)
-        const float zz = zj * zj;
-        const float h = -0.5f * zz;
-        const float hl = h - ls;
-        gauss = hl - HALF_LOG_2PI;
-        const float aa = a * a;
-        const float one = 1.0f - aa;
-        corr = logf(one + LOG_PROB_EPS);
-      }
     }
     X[r * S + D + j] = a;
     head[r * S + 16 + j] = gauss;

@@ -23,6 +23,7 @@
 #include "mjs_replay.h"
 #include "mjs_critic.h"
 #include "mjs_critic_train.h"
+#include "mjs_actor_train.h"
 #ifdef MJS_STAMPS
 #include "mjs_stamps_report.h"
 #endif
@@ -162,6 +163,19 @@ struct mjs_critic_opt {
   float* v = nullptr;
   float* slabs = nullptr;        // [max_splits][n_critics][L.total]
   float* gsum = nullptr;         // [n_critics][L.total]: the summed gradient on its way to nn.Linear layout
+  int64_t t = 0;                 // optimiser steps taken
+};
+
+// Adam on an actor's packed copy (mjs_actor_train.h): the moments, the slab workspace and the step count.
+struct mjs_actor_opt {
+  mjs_actor* actor = nullptr;    // the actor it was created for; must outlive the optimiser
+  mjs_actor_opt_desc desc;
+  crit::Layout L;
+  int max_splits = 0;            // slabs the workspace holds
+  float* m = nullptr;            // [L.total], slab layout
+  float* v = nullptr;
+  float* slabs = nullptr;        // [max_splits][L.total]
+  float* gsum = nullptr;         // [L.total]: the summed gradient on its way to nn.Linear layout
   int64_t t = 0;                 // optimiser steps taken
 };
 
@@ -1644,6 +1658,244 @@ int mjs_critic_export(const mjs_critic* q, const mjs_critic_weights* out, void* 
     const crit::Packed P = packed_of(q, c);
     launch_unpack(q, P.seg, c, out, (hipStream_t)stream);
   }
+  HIP_TRY(nullptr, hipGetLastError());
+  return MJS_OK;
+}
+
+// ---- the actor and entropy-coefficient update (mjs_actor_train.h) -------------------------------------------------------------
+// where an actor's layers sit in a slab (the stacked head in slot 3), and its packed copy as the segments' pointers
+static crit::Layout actor_layout_of(const mjs_actor* a) {
+  crit::Layout L{};
+  int at = 0, K = a->k0;
+  for (int l = 0; l < 4; l++) {
+    const bool used = l < a->desc.n_hidden || l == 3;
+    const int O = l == 3 ? act::OPAD : a->width[l];
+    L.off[2 * l] = at;
+    if (used) at += K * O;
+    L.off[2 * l + 1] = at;
+    if (used) at += O;
+    if (used && l < 3) K = O;
+  }
+  L.off[8] = at;
+  L.total = at + 4;
+  return L;
+}
+static crit::Packed actor_packed_of(const mjs_actor* a) {
+  crit::Packed P;
+  for (int l = 0; l < 4; l++) { P.seg[2 * l] = a->w[l]; P.seg[2 * l + 1] = a->b[l]; }
+  return P;
+}
+static bool actor_layers_given(const mjs_actor* a, const mjs_actor_weights* w) {
+  for (int l = 0; l < a->desc.n_hidden; l++)
+    if (!w->hidden_w[l] || !w->hidden_b[l]) return false;
+  return w->mu_w && w->mu_b && w->log_std_w && w->log_std_b;
+}
+// packed layers (the segments of the actor's copy or of a summed slab) -> nn.Linear layout: one launch per hidden layer, two for the head
+// (mu = the head's columns 0..A-1, log_std = A..2A-1)
+static void launch_actor_unpack(const mjs_actor* a, const float* const* seg, const mjs_actor_weights* out, hipStream_t s) {
+  int in = a->desc.in_dim, K = a->k0;
+  const int A = a->desc.action_dim;
+  for (int l = 0; l < a->desc.n_hidden; l++) {
+    crit::UnpackParams p;
+    p.src_w = seg[2 * l]; p.src_b = seg[2 * l + 1];
+    p.K = K; p.O = a->width[l];
+    p.in = in; p.out = a->desc.hidden[l];
+    p.dst_w = const_cast<float*>(out->hidden_w[l]);
+    p.dst_b = const_cast<float*>(out->hidden_b[l]);
+    crit::unpack_kernel<<<dim3((unsigned)((p.out * p.in + 255) / 256)), 256, 0, s>>>(p);
+    in = a->desc.hidden[l]; K = a->width[l];
+  }
+  for (int half = 0; half < 2; half++) {
+    crit::UnpackParams p;
+    p.src_w = seg[6] + half * A; p.src_b = seg[7] + half * A;
+    p.K = K; p.O = act::OPAD;
+    p.in = in; p.out = A;
+    p.dst_w = const_cast<float*>(half ? out->log_std_w : out->mu_w);
+    p.dst_b = const_cast<float*>(half ? out->log_std_b : out->mu_b);
+    crit::unpack_kernel<<<dim3((unsigned)((p.out * p.in + 255) / 256)), 256, 0, s>>>(p);
+  }
+}
+
+int mjs_actor_opt_create(mjs_actor* a, const mjs_actor_opt_desc* desc, mjs_actor_opt** out) {
+  const std::string name = "mjs_actor_opt_create";
+  const auto refuse = [&](const std::string& why) { return fail(nullptr, MJS_ERR_INVALID_ARG, name + ": " + why); };
+  if (out) *out = nullptr;
+  if (!a || !desc || !out) return refuse("null argument");
+  if (desc->struct_size != sizeof(mjs_actor_opt_desc)) return refuse("mjs_actor_opt_desc.struct_size does not match this library's header");
+  if (a->visual) return refuse("the actor reads feature blocks (mjs_actor_create_visual): the visual actor's update is not built");
+  if (!a->loaded) return refuse("the actor has no parameters yet (mjs_actor_load)");
+  if (!(desc->lr >= 0.0) || !std::isfinite(desc->lr)) return refuse("lr must be finite and >= 0");
+  if (!(desc->beta1 >= 0.0 && desc->beta1 < 1.0) || !(desc->beta2 >= 0.0 && desc->beta2 < 1.0)) return refuse("beta1 and beta2 must lie in [0, 1)");
+  if (!(desc->eps > 0.0) || !std::isfinite(desc->eps)) return refuse("eps must be finite and > 0");
+  DeviceGuard dev_(a->desc.device);
+  std::unique_ptr<mjs_actor_opt, void (*)(mjs_actor_opt*)> guard(new (std::nothrow) mjs_actor_opt(), mjs_actor_opt_destroy);
+  mjs_actor_opt* o = guard.get();
+  if (!o) return fail(nullptr, MJS_ERR_ALLOC, name + ": out of host memory");
+  CREATE_TRY(name, dev_.err);
+  o->actor = a;
+  o->desc = *desc;
+  o->L = actor_layout_of(a);
+  o->max_splits = crit::splits_max(1, o->L.total);
+  const size_t per = sizeof(float) * (size_t)o->L.total;
+  CREATE_TRY(name, hipMalloc(&o->m, per));
+  CREATE_TRY(name, hipMalloc(&o->v, per));
+  CREATE_TRY(name, hipMalloc(&o->gsum, per));
+  CREATE_TRY(name, hipMalloc(&o->slabs, per * o->max_splits));
+  CREATE_TRY(name, hipMemset(o->m, 0, per));
+  CREATE_TRY(name, hipMemset(o->v, 0, per));
+  CREATE_TRY(name, hipDeviceSynchronize());  // the moments are zero before any stream's first step
+  // X, three actor images, three critic images and the gradient pair at the widest stride, and the two critics' action gradients:
+  // an opt-in, below the CU's 160 KB
+  static_assert(atrain::lds_bytes(act::MAX_LAYERS, act::MAX_LAYERS, act::MAX_HIDDEN) <= 160 * 1024, "LDS images of atrain::grad_kernel");
+  CREATE_TRY(name, hipFuncSetAttribute(reinterpret_cast<const void*>(&atrain::grad_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       (int)atrain::lds_bytes(act::MAX_LAYERS, act::MAX_LAYERS, act::MAX_HIDDEN)));
+  *out = guard.release();
+  return MJS_OK;
+}
+
+void mjs_actor_opt_destroy(mjs_actor_opt* o) {
+  if (!o) return;
+  free_all({o->m, o->v, o->slabs, o->gsum});
+  delete o;
+}
+
+uint64_t mjs_actor_train_workspace_bytes(const mjs_actor* a, int32_t B) {
+  if (!a || a->visual || B <= 0) return 0;
+  const crit::Layout L = actor_layout_of(a);
+  return (uint64_t)crit::split_rule(B, 1, L.total).splits * L.total * sizeof(float);
+}
+
+// what mjs_actor_grad and mjs_actor_update refuse alike; "" = fine
+static std::string actor_grad_refusal(const mjs_actor* a, const mjs_actor_opt* o, const mjs_actor_grad_args* args) {
+  if (!a || !o || !args) return "actor, optimiser or args is null";
+  if (args->struct_size != sizeof(mjs_actor_grad_args)) return "mjs_actor_grad_args.struct_size does not match this library's header";
+  if (o->actor != a) return "the optimiser was created for another actor";
+  if (a->visual) return "the actor reads feature blocks (mjs_actor_create_visual): the visual actor's update is not built";
+  const mjs_critic* q = args->critic;
+  if (!q) return "critic is null";
+  if (a->desc.device != q->desc.device) return "the actor lives on another device than the critic";
+  if (!a->loaded) return "the actor has no parameters yet (mjs_actor_load)";
+  if (!q->loaded) return "the critic has no parameters yet (mjs_critic_load)";
+  if (a->desc.in_dim != q->desc.obs_dim) return "the actor's in_dim is not the critic's obs_dim";
+  if (a->desc.action_dim != q->desc.action_dim) return "the actor's action_dim is not the critic's";
+  if (args->B < 0) return "B is negative";
+  if (args->B > 0 && (!args->obs_dev || !args->z_dev)) return "obs_dev or z_dev is null";
+  if (const mjs_entropy_step* e = args->entropy) {
+    if (e->struct_size != sizeof(mjs_entropy_step)) return "mjs_entropy_step.struct_size does not match this library's header";
+    if (!e->log_ent_coef_dev || !e->ent_coef_dev || !e->m_dev || !e->v_dev) return "entropy: log_ent_coef_dev, ent_coef_dev, m_dev or v_dev is null";
+    if (!(e->lr >= 0.0) || !std::isfinite(e->lr)) return "entropy: lr must be finite and >= 0";
+    if (e->t < 1) return "entropy: t must be >= 1 (the step count after this step)";
+    if (!(e->beta1 >= 0.0 && e->beta1 < 1.0) || !(e->beta2 >= 0.0 && e->beta2 < 1.0)) return "entropy: beta1 and beta2 must lie in [0, 1)";
+    if (!(e->eps > 0.0) || !std::isfinite(e->eps)) return "entropy: eps must be finite and > 0";
+    if (!std::isfinite(e->target_entropy)) return "entropy: target_entropy must be finite";
+  }
+  return "";
+}
+// the gradient launch into the optimiser's slabs; returns the splits it wrote
+static int launch_actor_grad(const mjs_actor* a, mjs_actor_opt* o, const mjs_actor_grad_args* args, hipStream_t s) {
+  const mjs_critic* q = args->critic;
+  const crit::Split sp = crit::split_rule(args->B, 1, o->L.total);
+  const int widest = a->widest > q->widest ? a->widest : q->widest;  // one stride for the actor's and the critics' layers
+  atrain::GradParams p{};
+  p.c = critic_params(q, args->B, widest);
+  p.actor = mlp_of(nullptr, 0, a);
+  p.L = o->L;
+  p.tiles_per_split = sp.tiles_per_split;
+  p.inv_B = (float)(1.0 / (double)args->B);
+  p.obs = args->obs_dev; p.z = args->z_dev;
+  p.ent_coef = (float)args->ent_coef; p.ent_coef_dev = args->ent_coef_dev;
+  p.target_entropy = args->entropy ? (float)args->entropy->target_entropy : 0.0f;
+  p.actions = args->actions_out_dev; p.log_prob = args->log_prob_out_dev; p.q_pi = args->q_pi_out_dev; p.dq_da = args->min_q_action_grad_out_dev;
+  p.slabs = o->slabs;
+  atrain::grad_kernel<<<dim3((unsigned)sp.splits), act::WAVES * 64, atrain::lds_bytes(a->desc.n_hidden, q->desc.n_hidden, widest), s>>>(p);
+  return sp.splits;
+}
+static crit::SumParams actor_sum_params(const mjs_actor_opt* o, const mjs_actor_grad_args* args, int splits) {
+  crit::SumParams p{};
+  p.L = o->L; p.n_critics = 1; p.splits = splits;
+  p.inv_B = (float)(1.0 / (double)args->B);
+  p.slabs = o->slabs; p.loss = args->loss_out_dev;
+  return p;
+}
+
+int mjs_actor_grad(const mjs_actor* a, mjs_actor_opt* o, const mjs_actor_grad_args* args, void* stream) {
+  const auto refuse = [](const std::string& why) { return fail(nullptr, MJS_ERR_INVALID_ARG, "mjs_actor_grad: " + why); };
+  const std::string why = actor_grad_refusal(a, o, args);
+  if (!why.empty()) return refuse(why);
+  if (args->grads_out) {
+    if (args->grads_out->struct_size != sizeof(mjs_actor_weights)) return refuse("mjs_actor_weights.struct_size does not match this library's header");
+    if (!actor_layers_given(a, args->grads_out)) return refuse("grads_out: a layer's weight or bias pointer is null");
+  }
+  if (args->B == 0) return MJS_OK;
+  DeviceGuard dev_(a->desc.device);
+  HIP_TRY(nullptr, dev_.err);
+  const hipStream_t s = (hipStream_t)stream;
+  const int splits = launch_actor_grad(a, o, args, s);
+  if (args->loss_out_dev || args->grads_out)
+    crit::slab_sum_kernel<<<dim3((unsigned)((o->L.off[8] + 1 + 255) / 256), 1), 256, 0, s>>>(actor_sum_params(o, args, splits), o->gsum);
+  if (args->grads_out) {
+    const float* seg[8];
+    for (int k = 0; k < 8; k++) seg[k] = o->gsum + o->L.off[k];
+    launch_actor_unpack(a, seg, args->grads_out, s);
+  }
+  HIP_TRY(nullptr, hipGetLastError());
+  return MJS_OK;
+}
+
+int mjs_actor_update(mjs_actor_opt* o, const mjs_actor_grad_args* args, double lr, void* stream) {
+  const auto refuse = [](const std::string& why) { return fail(nullptr, MJS_ERR_INVALID_ARG, "mjs_actor_update: " + why); };
+  const std::string why = actor_grad_refusal(o ? o->actor : nullptr, o, args);
+  if (!why.empty()) return refuse(why);
+  if (!(lr >= 0.0) || !std::isfinite(lr)) return refuse("lr must be finite and >= 0");
+  if (args->grads_out) return refuse("grads_out must be null (mjs_actor_grad returns gradients)");
+  if (args->B == 0) return MJS_OK;
+  mjs_actor* a = o->actor;
+  DeviceGuard dev_(a->desc.device);
+  HIP_TRY(nullptr, dev_.err);
+  const hipStream_t s = (hipStream_t)stream;
+  const int splits = launch_actor_grad(a, o, args, s);
+  const double t = (double)(o->t + 1);
+  crit::AdamParams p{};
+  p.s = actor_sum_params(o, args, splits);
+  p.net[0] = actor_packed_of(a);
+  p.m = o->m; p.v = o->v;
+  p.one_minus_beta1 = (float)(1.0 - o->desc.beta1);
+  p.beta2 = (float)o->desc.beta2;
+  p.one_minus_beta2 = (float)(1.0 - o->desc.beta2);
+  p.sqrt_bc2 = (float)std::sqrt(1.0 - std::pow(o->desc.beta2, t));
+  p.eps = (float)o->desc.eps;
+  p.step_size = (float)(lr / (1.0 - std::pow(o->desc.beta1, t)));
+  crit::adam_kernel<<<dim3((unsigned)((o->L.off[8] + 1 + 255) / 256), 1), 256, 0, s>>>(p);
+  if (const mjs_entropy_step* e = args->entropy) {
+    const double te = (double)e->t;
+    atrain::EntParams ep{};
+    ep.slabs = o->slabs; ep.splits = splits; ep.total = o->L.total; ep.at = o->L.off[8] + 1;
+    ep.inv_B = (float)(1.0 / (double)args->B);
+    ep.log_ent_coef = e->log_ent_coef_dev; ep.ent_coef = e->ent_coef_dev; ep.m = e->m_dev; ep.v = e->v_dev;
+    ep.one_minus_beta1 = (float)(1.0 - e->beta1);
+    ep.beta2 = (float)e->beta2;
+    ep.one_minus_beta2 = (float)(1.0 - e->beta2);
+    ep.sqrt_bc2 = (float)std::sqrt(1.0 - std::pow(e->beta2, te));
+    ep.eps = (float)e->eps;
+    ep.step_size = (float)(e->lr / (1.0 - std::pow(e->beta1, te)));
+    atrain::ent_kernel<<<dim3(1), 64, 0, s>>>(ep);
+  }
+  HIP_TRY(nullptr, hipGetLastError());
+  o->t += 1;
+  return MJS_OK;
+}
+
+int mjs_actor_export(const mjs_actor* a, const mjs_actor_weights* out, void* stream) {
+  const auto refuse = [](const std::string& why) { return fail(nullptr, MJS_ERR_INVALID_ARG, "mjs_actor_export: " + why); };
+  if (!a || !out) return refuse("null argument");
+  if (out->struct_size != sizeof(mjs_actor_weights)) return refuse("mjs_actor_weights.struct_size does not match this library's header");
+  if (a->visual) return refuse("the actor reads feature blocks (mjs_actor_create_visual): its first layer has no nn.Linear counterpart here");
+  if (!a->loaded) return refuse("the actor has no parameters yet (mjs_actor_load)");
+  if (!actor_layers_given(a, out)) return refuse("a layer's weight or bias pointer is null");
+  DeviceGuard dev_(a->desc.device);
+  HIP_TRY(nullptr, dev_.err);
+  const crit::Packed P = actor_packed_of(a);
+  launch_actor_unpack(a, P.seg, out, (hipStream_t)stream);
   HIP_TRY(nullptr, hipGetLastError());
   return MJS_OK;
 }

@@ -412,21 +412,79 @@ class DeviceActor(_NativeObject):
 
     # ------------------------------------------------------------------ use
     def load(self):
-        """Pack the modules' current parameters into the library's copy (small kernels on the current stream, no synchronisation)."""
+        """Pack the modules' current parameters into the library's copy (small kernels on the current stream, no synchronisation).
+
+        Once a :class:`DeviceActorOptimizer` has stepped this actor, the packed copy is the master copy and the modules are stale:
+        ``load()`` would overwrite the trained parameters with them. :meth:`export` is the way back into torch."""
         if self._a is None:
             raise nat.MjsError("the actor is closed")
         self._check_modules()
         staged = [t.detach().contiguous() for m in (*self.hidden, self.mu, self.log_std) for t in (m.weight, m.bias)]
-        n = len(self.hidden)
-        w = nat.MjsActorWeights(hidden_w=(C.c_void_p * 3)(*[staged[2 * i].data_ptr() for i in range(n)]),
-                                hidden_b=(C.c_void_p * 3)(*[staged[2 * i + 1].data_ptr() for i in range(n)]),
-                                mu_w=staged[2 * n].data_ptr(), mu_b=staged[2 * n + 1].data_ptr(),
-                                log_std_w=staged[2 * n + 2].data_ptr(), log_std_b=staged[2 * n + 3].data_ptr())
+        w = self._weights_struct(staged)
         stream = torch.cuda.current_stream(self.device).cuda_stream
         nat.check(self._lib.mjs_actor_load(self._a, C.byref(w), C.c_void_p(stream)))
         self._staged = staged  # alive until the next load: the pack kernels read them asynchronously
         for e in self._owned_encoders:
             e.load()
+
+    def _weights_struct(self, tensors):
+        """mjs_actor_weights over the flat list (weight, bias) per hidden layer, then mu's and log_std's."""
+        n = len(self.hidden)
+        return nat.MjsActorWeights(hidden_w=(C.c_void_p * 3)(*[tensors[2 * i].data_ptr() for i in range(n)]),
+                                   hidden_b=(C.c_void_p * 3)(*[tensors[2 * i + 1].data_ptr() for i in range(n)]),
+                                   mu_w=tensors[2 * n].data_ptr(), mu_b=tensors[2 * n + 1].data_ptr(),
+                                   log_std_w=tensors[2 * n + 2].data_ptr(), log_std_b=tensors[2 * n + 3].data_ptr())
+
+    def _empty_like_parameters(self):
+        """Fresh contiguous float32 tensors in ``nn.Linear`` shapes: the flat list (weight, bias) per hidden layer, then mu's and log_std's."""
+        out, fan_in = [], self.in_total
+        for width in self.widths:
+            out += [torch.empty(width, fan_in, dtype=torch.float32, device=self.device), torch.empty(width, dtype=torch.float32, device=self.device)]
+            fan_in = width
+        for _ in range(2):
+            out += [torch.empty(self.action_dim, fan_in, dtype=torch.float32, device=self.device), torch.empty(self.action_dim, dtype=torch.float32, device=self.device)]
+        return out
+
+    def _check_export_modules(self, modules):
+        """(hidden, mu, log_std) with this actor's shapes, float32 on its device; ValueError otherwise."""
+        try:
+            hidden, mu, log_std = modules
+            hidden = list(hidden)
+        except (TypeError, ValueError):
+            raise ValueError("modules must be (hidden layers, mu, log_std), as DeviceActor.from_linears takes them") from None
+        if len(hidden) != len(self.widths):
+            raise ValueError(f"modules hold {len(hidden)} hidden layers, this actor {len(self.widths)}")
+        fan_in = self.in_total
+        for name, m, width in [(f"hidden[{i}]", m, w) for i, (m, w) in enumerate(zip(hidden, self.widths))] + [("mu", mu, self.action_dim), ("log_std", log_std, self.action_dim)]:
+            if not _is_linear(m):
+                raise ValueError(f"{name}: {type(m).__name__} is not a Linear layer (weight, bias, in_features, out_features)")
+            _check_parameters(name, m, "Linear", "actor", self.device)
+            if name in ("mu", "log_std"):
+                fan_in = self.widths[-1]
+            if tuple(m.weight.shape) != (width, fan_in) or tuple(m.bias.shape) != (width,):
+                raise ValueError(f"{name}: weight {tuple(m.weight.shape)} / bias {tuple(m.bias.shape)}, expected {(width, fan_in)} / {(width,)}")
+            fan_in = width
+        return hidden, mu, log_std
+
+    def export(self, modules=None):
+        """The packed parameters into ``modules = (hidden, mu, log_std)`` of ``torch.nn.Linear`` (default: the modules this object was
+        made from), with ``copy_`` under ``no_grad``: the way back into torch after steps of a :class:`DeviceActorOptimizer`. Small
+        kernels on the current stream, no synchronisation. Returns ``(hidden, mu, log_std)``. State actors only."""
+        if self.visual:
+            raise ValueError("a visual actor: its update is not built, and its first layer has no single nn.Linear input here")
+        hidden, mu, log_std = self._check_export_modules((self.hidden, self.mu, self.log_std) if modules is None else modules)
+        if self._a is None:
+            raise nat.MjsError("the actor is closed")
+        staged = self._empty_like_parameters()
+        w = self._weights_struct(staged)
+        launch = self._lib.mjs_actor_export
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        nat.check(launch(self._a, C.byref(w), C.c_void_p(stream)))
+        with torch.no_grad():
+            for k, m in enumerate((*hidden, mu, log_std)):
+                m.weight.copy_(staged[2 * k])
+                m.bias.copy_(staged[2 * k + 1])
+        return hidden, mu, log_std
 
     def close(self):
         super().close()
@@ -438,8 +496,8 @@ class DeviceCritic(_NativeObject):
     """SAC's critics (SB3's ``ContinuousCritic``: ``n_critics`` MLPs over ``[obs | action]`` with a scalar head) held by libmjsim.so
     for one device (csrc/mjs_critic.h). :meth:`q_values` and :func:`sac_td_target` take no gradient; the critic loss, its gradients
     and the Adam step run on the packed copy through :class:`DeviceCriticOptimizer` (csrc/mjs_critic_train.h), a target critic follows
-    with :meth:`blend_from`, and :meth:`export` writes the trained parameters back into torch modules for the actor loss, which stays
-    in torch. float32 with float32 accumulation, like :class:`DeviceActor`.
+    with :meth:`blend_from`, the actor loss reads the packed copy through :class:`DeviceActorOptimizer` (csrc/mjs_actor_train.h), and
+    :meth:`export` writes the trained parameters back into torch modules. float32 with float32 accumulation, like :class:`DeviceActor`.
 
     The object keeps references to the torch modules it was made from; :meth:`load` packs their CURRENT parameters, or blends those
     of other modules of the same shapes into the packed copy (``tau < 1``: SB3's ``polyak_update``), so that a TARGET critic can
@@ -852,3 +910,262 @@ def sac_td_target(batch, actor, critic, gamma, ent_coef, z=None, generator=None,
         stream = torch.cuda.current_stream(dev).cuda_stream
         nat.check(launch(actor._a, critic._q, C.byref(args), C.c_void_p(stream)))
     return out if return_parts else out["target"]
+
+
+class DeviceEntropyCoef:
+    """SB3's learned entropy coefficient (``ent_coef="auto"``) as one small device tensor: ``log_ent_coef``, ``ent_coef = exp(log_ent_coef)``
+    and Adam's two moments, plus the step count on the host. :meth:`DeviceActorOptimizer.step` updates it in the same call, after its old
+    value was used (csrc/mjs_actor_train.h ent_kernel)::
+
+        ent_coef_loss = -(log_ent_coef * (log_prob + target_entropy).detach()).mean();  Adam step on log_ent_coef
+
+    ``.ent_coef`` is the one-element device view :func:`sac_td_target` accepts; nothing is ever read back. ``init`` is SB3's
+    ``ent_coef="auto_<init>"`` (default 1.0), ``target_entropy`` defaults to ``-action_dim``."""
+
+    def __init__(self, device, action_dim, init=1.0, lr=3e-4, target_entropy=None, betas=(0.9, 0.999), eps=1e-8):
+        try:
+            action_dim, init = int(action_dim), float(init)
+        except (TypeError, ValueError):
+            raise ValueError("action_dim must be an int and init a float") from None
+        if not 1 <= action_dim <= nat.ACTOR_MAX_ACTIONS:
+            raise ValueError(f"action_dim must lie in 1..{nat.ACTOR_MAX_ACTIONS}, got {action_dim}")
+        if not 0.0 < init < float("inf"):
+            raise ValueError(f"init must be positive and finite, got {init}")
+        self.lr = DeviceCriticOptimizer._checked_lr(lr)
+        try:
+            beta1, beta2 = (float(b) for b in betas)
+        except (TypeError, ValueError):
+            raise ValueError("betas must be two floats in [0, 1)") from None
+        if not (0.0 <= beta1 < 1.0 and 0.0 <= beta2 < 1.0):
+            raise ValueError(f"betas must lie in [0, 1), got {(beta1, beta2)}")
+        eps = float(eps)
+        if not 0.0 < eps < float("inf"):
+            raise ValueError(f"eps must be positive and finite, got {eps}")
+        self.betas, self.eps = (beta1, beta2), eps
+        try:
+            self.target_entropy = float(-action_dim if target_entropy is None else target_entropy)
+        except (TypeError, ValueError):
+            raise ValueError("target_entropy must be a float") from None
+        if self.target_entropy != self.target_entropy or abs(self.target_entropy) == float("inf"):
+            raise ValueError(f"target_entropy must be finite, got {self.target_entropy}")
+        self.action_dim = action_dim
+        self.device = torch.device(device if not isinstance(device, int) else f"cuda:{device}")
+        if self.device.type == "cuda" and self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        log_init = torch.log(torch.ones(1, dtype=torch.float32) * init)  # SB3: th.log(th.ones(1) * init_value)
+        self._state = torch.cat([log_init, log_init.exp(), torch.zeros(2)]).to(self.device)  # log_ent_coef, ent_coef, m, v
+        self.step_count = 0
+
+    @property
+    def log_ent_coef(self):
+        return self._state[0:1]
+
+    @property
+    def ent_coef(self):
+        return self._state[1:2]
+
+    def _block(self, lr=None):
+        """mjs_entropy_step for the NEXT step (t = step_count + 1)."""
+        base = self._state.data_ptr()
+        return nat.MjsEntropyStep(log_ent_coef_dev=base, ent_coef_dev=base + 4, m_dev=base + 8, v_dev=base + 12, t=self.step_count + 1,
+                                  lr=self.lr if lr is None else lr, beta1=self.betas[0], beta2=self.betas[1], eps=self.eps, target_entropy=self.target_entropy)
+
+
+class DeviceActorOptimizer(_NativeObject):
+    """The actor update of SB3's ``SAC.train`` on a :class:`DeviceActor`'s packed parameters (csrc/mjs_actor_train.h)::
+
+        a, log_prob = actor.action_log_prob(obs)
+        actor_loss = (ent_coef * log_prob - min_c Q_c(obs, a)).mean()
+        actor.optimizer.zero_grad(); actor_loss.backward(); actor.optimizer.step()            # torch.optim.Adam, SB3's defaults
+
+    as two launches per :meth:`step` (three with a learned entropy coefficient): the forward pass of the actor and the critics, the backward
+    pass through the critics' inputs and the actor with a bitwise reproducible sum over the batch, then Adam. The critics are only read.
+    The packed copy is the master copy from the first step on: ``venv.actor_actions``, ``venv.actor_rollout`` and :func:`sac_td_target`
+    see every step at once, ``actor.export()`` refreshes the torch modules, and ``actor.load()`` would overwrite the trained parameters
+    with the stale modules. The optimiser keeps the actor alive."""
+    _handle, _destroy = "_o", "mjs_actor_opt_destroy"
+
+    def __init__(self, actor, lr=3e-4, betas=(0.9, 0.999), eps=1e-8):
+        self._o = None
+        if not isinstance(actor, DeviceActor):
+            raise ValueError(f"actor must be a DeviceActor, got {type(actor).__name__}")
+        if actor.visual:
+            raise ValueError("a visual actor: its update is not built (state observations only)")
+        self.lr = DeviceCriticOptimizer._checked_lr(lr)
+        try:
+            beta1, beta2 = (float(b) for b in betas)
+        except (TypeError, ValueError):
+            raise ValueError("betas must be two floats in [0, 1)") from None
+        if not (0.0 <= beta1 < 1.0 and 0.0 <= beta2 < 1.0):
+            raise ValueError(f"betas must lie in [0, 1), got {(beta1, beta2)}")
+        eps = float(eps)
+        if not 0.0 < eps < float("inf"):
+            raise ValueError(f"eps must be positive and finite, got {eps}")
+        self.betas, self.eps = (beta1, beta2), eps
+        self.actor, self.device = actor, actor.device
+        self.step_count = 0
+        if actor._a is None:
+            raise nat.MjsError("the actor is closed")
+        # ---- native from here on
+        self._lib = actor._lib
+        desc = nat.MjsActorOptDesc(lr=self.lr, beta1=beta1, beta2=beta2, eps=eps)
+        o = C.c_void_p()
+        nat.check(self._lib.mjs_actor_opt_create(actor._a, C.byref(desc), C.byref(o)))
+        self._o = o
+
+    def _checked(self, batch, critic, ent_coef, z):
+        """(obs, B, ent_coef float, ent_coef tensor or None, DeviceEntropyCoef or None) checked; ValueError before anything native."""
+        from .replay import _want
+
+        a = self.actor
+        if not isinstance(critic, DeviceCritic):
+            raise ValueError(f"critic must be a DeviceCritic, got {type(critic).__name__}")
+        if a.device != critic.device:
+            raise ValueError(f"the actor lives on {a.device}, the critic on {critic.device}")
+        if a.in_dim != critic.obs_dim:
+            raise ValueError(f"the actor reads {a.in_dim} observation columns, the critic {critic.obs_dim}")
+        if a.action_dim != critic.action_dim:
+            raise ValueError(f"the actor has {a.action_dim} action components, the critic {critic.action_dim}")
+        if not isinstance(batch, dict) or "obs" not in batch:
+            raise ValueError("batch must be a dict with 'obs' (DeviceReplayBuffer.sample's result)")
+        obs = batch["obs"]
+        if not isinstance(obs, torch.Tensor) or obs.dim() != 2:
+            raise ValueError("batch['obs'] must be a float32 tensor [B, obs_dim]")
+        B = int(obs.shape[0])
+        _want("batch['obs']", obs, (B, a.in_dim), torch.float32, self.device)
+        learned = ent_dev = None
+        if isinstance(ent_coef, DeviceEntropyCoef):
+            if ent_coef.device != self.device:
+                raise ValueError(f"the entropy coefficient lives on {ent_coef.device}, the actor on {self.device}")
+            if ent_coef.action_dim != a.action_dim:
+                raise ValueError(f"the entropy coefficient was made for {ent_coef.action_dim} action components, the actor has {a.action_dim}")
+            learned, ent_dev, ent = ent_coef, ent_coef.ent_coef, 0.0
+        elif isinstance(ent_coef, torch.Tensor):
+            ent_dev = _want("ent_coef", ent_coef, tuple(ent_coef.shape) if ent_coef.numel() == 1 and ent_coef.dim() <= 1 else (1,), torch.float32, self.device)
+            ent = 0.0
+        else:
+            try:
+                ent = float(ent_coef)
+            except (TypeError, ValueError):
+                raise ValueError(f"ent_coef must be a float, a one-element float32 tensor or a DeviceEntropyCoef, got {type(ent_coef).__name__}") from None
+        if z is not None:
+            _want("z", z, (B, a.action_dim), torch.float32, self.device)
+        return obs, B, ent, ent_dev, learned
+
+    def _open(self, critic):
+        if self.actor._a is None:
+            raise nat.MjsError("the actor is closed")
+        critic._open()
+        if self._o is None:
+            raise nat.MjsError("the optimiser is closed")
+
+    def _parts(self, critic, B):
+        dev, A = self.device, self.actor.action_dim
+        return {"actions": torch.empty(B, A, dtype=torch.float32, device=dev), "log_prob": torch.empty(B, dtype=torch.float32, device=dev),
+                "q_pi": torch.empty(critic.n_critics, B, dtype=torch.float32, device=dev),
+                "min_q_action_grad": torch.empty(B, A, dtype=torch.float32, device=dev), "loss": torch.zeros(1, dtype=torch.float32, device=dev)}
+
+    @staticmethod
+    def _args(obs, z, critic, B, ent, ent_dev, parts, grads=None, entropy=None):
+        ptr = lambda k: parts[k].data_ptr() if parts is not None else None  # noqa: E731
+        return nat.MjsActorGradArgs(B=B, obs_dev=obs.data_ptr(), z_dev=z.data_ptr(), critic=critic._q, ent_coef=ent,
+                                    ent_coef_dev=ent_dev.data_ptr() if ent_dev is not None else None, actions_out_dev=ptr("actions"),
+                                    log_prob_out_dev=ptr("log_prob"), q_pi_out_dev=ptr("q_pi"), min_q_action_grad_out_dev=ptr("min_q_action_grad"),
+                                    loss_out_dev=ptr("loss"), grads_out=C.pointer(grads) if grads is not None else None,
+                                    entropy=C.pointer(entropy) if entropy is not None else None)
+
+    def step(self, batch, critic, ent_coef, z=None, generator=None, lr=None, return_parts=False):
+        """One gradient step of the actor on ``batch['obs']`` (float32 [B, obs_dim]; the batch's columns are the actor's inputs, in order)
+        through ``critic`` (the ONLINE :class:`DeviceCritic`, after its own step). ``ent_coef``: a float, a one-element float32 device tensor, or
+        a :class:`DeviceEntropyCoef`, which is updated by the same call AFTER its old value was used for both losses, as SB3 does.
+        ``z``: float32 [B, A] standard-normal draws (default ``torch.randn(B, A, generator=generator)`` on the device). ``lr``: this step's
+        learning rate for the actor (default: the constructor's). Two or three launches on the current stream; nothing is read back.
+        Returns ``None``, or with ``return_parts`` a dict with ``actions`` [B, A], ``log_prob`` [B], ``q_pi`` [n_critics, B],
+        ``min_q_action_grad`` [B, A] and ``loss`` [1] (the actor loss BEFORE the step). An empty batch does nothing and is not counted."""
+        obs, B, ent, ent_dev, learned = self._checked(batch, critic, ent_coef, z)
+        lr = self.lr if lr is None else DeviceCriticOptimizer._checked_lr(lr)
+        self._open(critic)
+        parts = self._parts(critic, B) if return_parts else None
+        if B:
+            if z is None:
+                z = torch.randn(B, self.actor.action_dim, dtype=torch.float32, device=self.device, generator=generator)
+            block = learned._block() if learned is not None else None
+            args = self._args(obs, z, critic, B, ent, ent_dev, parts, entropy=block)
+            update = self._lib.mjs_actor_update
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            nat.check(update(self._o, C.byref(args), lr, C.c_void_p(stream)))
+            self.step_count += 1
+            if learned is not None:
+                learned.step_count += 1
+        return parts
+
+    def gradients(self, batch, critic, ent_coef, z):
+        """The gradients :meth:`step` would apply, and no update (a :class:`DeviceEntropyCoef` is read, not stepped): a dict with ``grads``
+        (a list of ``(weight_grad, bias_grad)`` in ``nn.Linear`` shapes: the hidden layers, then mu, then log_std) and the parts of
+        :meth:`step`."""
+        if z is None:
+            raise ValueError("z must be given: float32 [B, action_dim] standard-normal draws")
+        obs, B, ent, ent_dev, _ = self._checked(batch, critic, ent_coef, z)
+        self._open(critic)
+        parts = self._parts(critic, B)
+        flat = self.actor._empty_like_parameters()
+        if B:
+            args = self._args(obs, z, critic, B, ent, ent_dev, parts, grads=self.actor._weights_struct(flat))
+            grad = self._lib.mjs_actor_grad
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            nat.check(grad(self.actor._a, self._o, C.byref(args), C.c_void_p(stream)))
+        else:
+            for t in flat:
+                t.zero_()
+        return {"grads": [(flat[2 * k], flat[2 * k + 1]) for k in range(len(flat) // 2)], **parts}
+
+
+def sac_gradient_step(batch, actor, critic, target_critic, critic_opt, actor_opt, ent_coef, gamma, tau, z_next=None, z_pi=None, generator=None):
+    """One whole gradient step of SB3's ``SAC.train`` on the device, in SB3's order, with no native code of its own:
+
+    1. :func:`sac_td_target` on ``target_critic`` with the entropy coefficient from BEFORE this step;
+    2. ``critic_opt.step(batch, target)``;
+    3. ``actor_opt.step(batch, critic, ent_coef)``, which also moves a :class:`DeviceEntropyCoef`;
+    4. ``target_critic.blend_from(critic, tau)``.
+
+    ``batch``: :meth:`DeviceReplayBuffer.sample`'s dict. ``z_next`` / ``z_pi``: the standard-normal draws of the target's and the actor
+    loss's action samples (default: fresh ones from ``generator``, which both share: ``z_next`` is drawn first, in step 1, then ``z_pi``,
+    in step 3). Every argument check raises ``ValueError``, and a closed object ``MjsError``, before any native call; nothing is read back.
+    Returns ``None``."""
+    if not isinstance(critic_opt, DeviceCriticOptimizer):
+        raise ValueError(f"critic_opt must be a DeviceCriticOptimizer, got {type(critic_opt).__name__}")
+    if not isinstance(actor_opt, DeviceActorOptimizer):
+        raise ValueError(f"actor_opt must be a DeviceActorOptimizer, got {type(actor_opt).__name__}")
+    if critic_opt.critic is not critic:
+        raise ValueError("critic_opt was made for another critic")
+    if actor_opt.actor is not actor:
+        raise ValueError("actor_opt was made for another actor")
+    if not isinstance(target_critic, DeviceCritic):
+        raise ValueError(f"target_critic must be a DeviceCritic, got {type(target_critic).__name__}")
+    if target_critic is critic:
+        raise ValueError("target_critic and critic are one object")
+    if not isinstance(batch, dict) or any(k not in batch for k in ("obs", "actions", "next_obs", "rewards", "dones")):
+        raise ValueError("batch must be a dict with 'obs', 'actions', 'next_obs', 'rewards' and 'dones' (DeviceReplayBuffer.sample's result)")
+    tau = float(tau)
+    if not 0.0 < tau <= 1.0:
+        raise ValueError(f"tau must lie in (0, 1], got {tau}")
+    mine, theirs = (target_critic.obs_dim, target_critic.action_dim, target_critic.n_critics, target_critic.widths, target_critic.activation), \
+                   (critic.obs_dim, critic.action_dim, critic.n_critics, critic.widths, critic.activation)
+    if mine != theirs or target_critic.device != critic.device:
+        raise ValueError(f"the target critic differs from the critic: (obs_dim, action_dim, n_critics, widths, activation) {mine} against {theirs}")
+    # the remaining checks of the later calls, before the first launch
+    from .replay import _want
+
+    _, B, _, _, _ = actor_opt._checked(batch, critic, ent_coef, z_pi)
+    _want("batch['actions']", batch["actions"], (B, critic.action_dim), torch.float32, critic.device)
+    for name in ("next_obs", "rewards", "dones"):
+        if not isinstance(batch[name], torch.Tensor) or int(batch[name].shape[0] if batch[name].dim() else -1) != B:
+            raise ValueError(f"batch[{name!r}] must be a float32 tensor of {B} rows, as batch['obs']")
+    alpha = ent_coef.ent_coef if isinstance(ent_coef, DeviceEntropyCoef) else ent_coef
+    target_critic._open()
+    critic_opt._open()
+    actor_opt._open(critic)
+    target = sac_td_target(batch, actor, target_critic, gamma, alpha, z=z_next, generator=generator)  # (its own checks precede its launch)
+    critic_opt.step(batch, target)
+    actor_opt.step(batch, critic, ent_coef, z=z_pi, generator=generator)
+    target_critic.blend_from(critic, tau)
