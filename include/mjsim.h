@@ -707,6 +707,69 @@ int mjs_actor_update(mjs_actor_opt* opt, const mjs_actor_grad_args* args, double
  * visual actor or an actor never loaded. */
 int mjs_actor_export(const mjs_actor* actor, const mjs_actor_weights* weights_out, void* stream);
 
+/* SAC's gradient loop on the device (csrc/mjs_sac_train.h; entry points added after abi 3 as well): the batch and both action samples'
+ * draws of one gradient step from ONE launch, and G whole gradient steps of SAC.train from one call. The generator is counter based:
+ * Philox4x32-10 with key (seed & 0xffffffff, seed >> 32) and counter (b, block, step & 0xffffffff, step >> 32) for batch row b and
+ * gradient-step counter step. Block 0's words w0, w1 give draw = (((uint64) w0 << 32) | w1) >> 2, the int64 below 2^62 that
+ * mjs_replay_sample takes, and the ring row draw % min(count, capacity); blocks 1, 2 give z_next[b, 0..3] and [b, 4..7], blocks 3, 4
+ * z_pi likewise, by Box-Muller in float32 over the word pairs (w0, w1) and (w2, w3):
+ *   u1 = ((w >> 8) + 1) * 2^-24;  u2 = (w' >> 8) * 2^-24;  r = sqrtf(-2 * logf(u1));  pair = (r * cosf(2 pi u2), r * sinf(2 pi u2))
+ * Only components below action_dim are written. Nothing is read back and no other generator is involved: a (seed, step) pair names
+ * its batch. */
+typedef struct {
+  uint32_t struct_size;      /* sizeof(mjs_sac_batch) */
+  int32_t reserved0;         /* 0 */
+  int64_t* idx_out;          /* [B], required: the ring rows gathered, -1 while the buffer is empty (every gathered row is zero then) */
+  int64_t* draws_out;        /* [B] or NULL: the raw draws; mjs_replay_sample on them gathers the same rows */
+  float* obs;                /* [B, D], required where D > 0, like next_obs */
+  float* next_obs;           /* [B, D] */
+  float* actions;            /* [B, action_dim], required */
+  float* rewards;            /* [B], required */
+  float* dones;              /* [B], required */
+  float* z_next;             /* [B, action_dim], required: the draws of the target's action sample */
+  float* z_pi;               /* [B, action_dim], required: the draws of the actor loss's action sample */
+} mjs_sac_batch;             /* 80 bytes */
+/* One launch on the caller's stream. MJS_ERR_INVALID_ARG (nothing launched, text in mjs_last_error(NULL)) for a null argument or
+ * required pointer, a wrong struct_size, a storage mjs_replay_sample would refuse, a storage with cameras (the SAC update is state-only)
+ * or B < 0; B == 0 does nothing and returns 0. */
+int mjs_sac_draw_batch(const mjs_replay_storage* storage, const mjs_sac_batch* out, int32_t B, uint64_t seed, uint64_t step, void* stream);
+typedef struct {
+  uint32_t struct_size;                  /* sizeof(mjs_sac_train_args) */
+  int32_t B;                             /* batch rows: >= 1 */
+  int32_t G;                             /* gradient steps: >= 0 */
+  int32_t target_update_interval;        /* >= 1 */
+  const mjs_replay_storage* storage;     /* required: no cameras, obs_dim and action_dim the networks' */
+  mjs_actor* actor;                      /* required: loaded, of mjs_actor_create */
+  mjs_critic* critic;                    /* required: the online critic */
+  mjs_critic* target_critic;             /* required: another object of the same shape */
+  mjs_critic_opt* critic_opt;            /* required: created for critic */
+  mjs_actor_opt* actor_opt;              /* required: created for actor */
+  const mjs_sac_batch* batch;            /* required: the caller's scratch for B rows, overwritten by every step; draws_out may be NULL */
+  float* target_dev;                     /* [B], required: scratch for the TD target */
+  uint64_t seed;                         /* the generator's key */
+  uint64_t step0;                        /* the gradient-step counter of the first step; step g uses step0 + g */
+  double gamma;                          /* [0, 1] */
+  double tau;                            /* (0, 1] */
+  double critic_lr;                      /* >= 0 */
+  double actor_lr;                       /* >= 0 */
+  double ent_coef;                       /* the fixed coefficient; ignored where ent_coef_dev is given */
+  const float* ent_coef_dev;             /* one float32 on the device or NULL; with an entropy block, its ent_coef_dev */
+  const mjs_entropy_step* entropy;       /* NULL, or the learned coefficient's step; t is the count after the FIRST step, step g uses t + g */
+} mjs_sac_train_args;                    /* 152 bytes */
+/* G gradient steps with no return to the caller, as plain launches on the caller's stream (eight per step with a learned coefficient and a
+ * blending target: 1 + 1 + 2 + 3 + 1; no graph capture): for g = 0..G-1, through the entry points above and their unchanged kernels,
+ *   1. mjs_sac_draw_batch(seed, step0 + g) into batch
+ *   2. mjs_sac_td_target on target_critic with the coefficient from before the step, into target_dev
+ *   3. mjs_critic_update(critic_opt, critic_lr)
+ *   4. mjs_actor_update(actor_opt, actor_lr), with an entropy block the coefficient's step as well
+ *   5. mjs_critic_blend(target_critic, critic, tau) where (step0 + g + 1) % target_update_interval == 0
+ * Both optimisers' step counts advance by G. MJS_ERR_INVALID_ARG (nothing launched, text in mjs_last_error(NULL)) for a null argument
+ * or required pointer, a wrong struct_size, B < 1, G < 0, target_update_interval < 1, cameras in the storage, a storage whose obs_dim or
+ * action_dim is not the networks', objects on different devices, an optimiser of another network, target_critic == critic, tau outside
+ * (0, 1], gamma outside [0, 1], a negative lr, and anything one of the five entry points refuses: all of it is checked before the first
+ * launch. G == 0 does nothing and returns 0. */
+int mjs_sac_train(const mjs_sac_train_args* args, void* stream);
+
 /* Replaces the Robot entity's control API on a stand-alone UR5e (entities/robots/robot.py:198-272): Robot.moveJ :211-216,
  * Robot.movej_IK :198-209, Robot.servoL :218-225, Robot.servoJ :227-259, then n_substeps x (Robot.before_substep :261-272 +
  * JointTrajectory.get_target_joint_positions joint_trajectory.py:41-47; Physics.step), then Robot.get_tcp_pose :153-168.

@@ -22,6 +22,7 @@ from .policies import (DeviceActor, DeviceActorOptimizer, DeviceCritic, DeviceCr
                        sac_gradient_step, sac_td_target)
 from .recording import LeRobotDatasetRecorder  # noqa: F401
 from .replay import DeviceReplayBuffer  # noqa: F401
+from .sac import DeviceSAC  # noqa: F401
 from .vector_env import TASKS, HipVectorEnv  # noqa: F401
 
 __version__ = "0.1.0"

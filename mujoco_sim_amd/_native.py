@@ -55,6 +55,7 @@ EXPORTED_SYMBOLS = [
     "mjs_critic_opt_create", "mjs_critic_opt_destroy", "mjs_critic_train_workspace_bytes", "mjs_critic_grad", "mjs_critic_update", "mjs_critic_blend",
     "mjs_critic_export",
     "mjs_actor_opt_create", "mjs_actor_opt_destroy", "mjs_actor_train_workspace_bytes", "mjs_actor_grad", "mjs_actor_update", "mjs_actor_export",
+    "mjs_sac_draw_batch", "mjs_sac_train",
 ]
 
 
@@ -227,6 +228,22 @@ class MjsActorGradArgs(_Sized):
                 ("grads_out", C.POINTER(MjsActorWeights)), ("entropy", C.POINTER(MjsEntropyStep))]
 
 
+class MjsSacBatch(_Sized):
+    """mjs_sac_batch: where mjs_sac_draw_batch writes a gradient step's batch and draws (caller-owned scratch); draws_out may be NULL."""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved0", C.c_int32), ("idx_out", C.c_void_p), ("draws_out", C.c_void_p), ("obs", C.c_void_p),
+                ("next_obs", C.c_void_p), ("actions", C.c_void_p), ("rewards", C.c_void_p), ("dones", C.c_void_p), ("z_next", C.c_void_p),
+                ("z_pi", C.c_void_p)]
+
+
+class MjsSacTrainArgs(_Sized):
+    """mjs_sac_train_args: the objects, scratch buffers and hyperparameters of G gradient steps in one native call."""
+    _fields_ = [("struct_size", C.c_uint32), ("B", C.c_int32), ("G", C.c_int32), ("target_update_interval", C.c_int32),
+                ("storage", C.POINTER(MjsReplayStorage)), ("actor", C.c_void_p), ("critic", C.c_void_p), ("target_critic", C.c_void_p),
+                ("critic_opt", C.c_void_p), ("actor_opt", C.c_void_p), ("batch", C.POINTER(MjsSacBatch)), ("target_dev", C.c_void_p),
+                ("seed", C.c_uint64), ("step0", C.c_uint64), ("gamma", C.c_double), ("tau", C.c_double), ("critic_lr", C.c_double),
+                ("actor_lr", C.c_double), ("ent_coef", C.c_double), ("ent_coef_dev", C.c_void_p), ("entropy", C.POINTER(MjsEntropyStep))]
+
+
 class MjsError(RuntimeError):
     pass
 
@@ -381,6 +398,8 @@ def lib() -> C.CDLL:
     L.mjs_actor_grad.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(MjsActorGradArgs), C.c_void_p]
     L.mjs_actor_update.argtypes = [C.c_void_p, C.POINTER(MjsActorGradArgs), C.c_double, C.c_void_p]
     L.mjs_actor_export.argtypes = [C.c_void_p, C.POINTER(MjsActorWeights), C.c_void_p]
+    L.mjs_sac_draw_batch.argtypes = [C.POINTER(MjsReplayStorage), C.POINTER(MjsSacBatch), C.c_int32, C.c_uint64, C.c_uint64, C.c_void_p]
+    L.mjs_sac_train.argtypes = [C.POINTER(MjsSacTrainArgs), C.c_void_p]
     L.mjs_get_rng_state.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.mjs_set_rng_state.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = L

@@ -24,6 +24,7 @@
 #include "mjs_critic.h"
 #include "mjs_critic_train.h"
 #include "mjs_actor_train.h"
+#include "mjs_sac_train.h"
 #ifdef MJS_STAMPS
 #include "mjs_stamps_report.h"
 #endif
@@ -1404,21 +1405,26 @@ int mjs_critic_q(const mjs_critic* q, const float* obs_dev, const float* actions
   return MJS_OK;
 }
 
+// what mjs_sac_td_target refuses; "" = fine
+static std::string td_refusal(const mjs_actor* actor, const mjs_critic* q, const mjs_td_target_args* args) {
+  if (!actor || !q || !args) return "actor, critic or args is null";
+  if (args->struct_size != sizeof(mjs_td_target_args)) return "mjs_td_target_args.struct_size does not match this library's header";
+  if (actor->visual) return "the actor reads feature blocks (mjs_actor_create_visual): visual critics are not built";
+  if (actor->desc.device != q->desc.device) return "the actor lives on another device than the critic";
+  if (!actor->loaded) return "the actor has no parameters yet (mjs_actor_load)";
+  if (!q->loaded) return "the critic has no parameters yet (mjs_critic_load)";
+  if (actor->desc.in_dim != q->desc.obs_dim) return "the actor's in_dim is not the critic's obs_dim";
+  if (actor->desc.action_dim != q->desc.action_dim) return "the actor's action_dim is not the critic's";
+  if (args->B < 0) return "B is negative";
+  if (!(args->gamma >= 0.0 && args->gamma <= 1.0)) return "gamma must lie in [0, 1]";
+  if (args->B > 0 && (!args->next_obs_dev || !args->rewards_dev || !args->dones_dev || !args->z_dev || !args->target_out_dev))
+    return "next_obs_dev, rewards_dev, dones_dev, z_dev or target_out_dev is null";
+  return "";
+}
+
 int mjs_sac_td_target(const mjs_actor* actor, const mjs_critic* q, const mjs_td_target_args* args, void* stream) {
-  const auto refuse = [](const std::string& why) { return fail(nullptr, MJS_ERR_INVALID_ARG, "mjs_sac_td_target: " + why); };
-  if (!actor || !q || !args) return refuse("actor, critic or args is null");
-  if (args->struct_size != sizeof(mjs_td_target_args)) return refuse("mjs_td_target_args.struct_size does not match this library's header");
-  if (actor->visual) return refuse("the actor reads feature blocks (mjs_actor_create_visual): visual critics are not built");
-  if (actor->desc.device != q->desc.device) return refuse("the actor lives on another device than the critic");
-  if (!actor->loaded) return refuse("the actor has no parameters yet (mjs_actor_load)");
-  if (!q->loaded) return refuse("the critic has no parameters yet (mjs_critic_load)");
-  if (actor->desc.in_dim != q->desc.obs_dim) return refuse("the actor's in_dim is not the critic's obs_dim");
-  if (actor->desc.action_dim != q->desc.action_dim) return refuse("the actor's action_dim is not the critic's");
-  if (args->B < 0) return refuse("B is negative");
-  if (!(args->gamma >= 0.0 && args->gamma <= 1.0)) return refuse("gamma must lie in [0, 1]");
+  if (std::string why = td_refusal(actor, q, args); !why.empty()) return fail(nullptr, MJS_ERR_INVALID_ARG, "mjs_sac_td_target: " + why);
   if (args->B == 0) return MJS_OK;
-  if (!args->next_obs_dev || !args->rewards_dev || !args->dones_dev || !args->z_dev || !args->target_out_dev)
-    return refuse("next_obs_dev, rewards_dev, dones_dev, z_dev or target_out_dev is null");
   DeviceGuard dev_(q->desc.device);
   HIP_TRY(nullptr, dev_.err);
   const int widest = actor->widest > q->widest ? actor->widest : q->widest;  // one stride for the actor's and the critics' layers
@@ -1624,14 +1630,19 @@ int mjs_critic_update(mjs_critic_opt* o, const mjs_critic_grad_args* args, doubl
   return MJS_OK;
 }
 
+// what mjs_critic_blend refuses; "" = fine
+static std::string blend_refusal(const mjs_critic* dst, const mjs_critic* src, double tau) {
+  if (!dst || !src) return "null critic";
+  if (!same_shape(dst, src)) return "the two critics differ in shape";
+  if (dst->desc.device != src->desc.device) return "the two critics live on different devices";
+  if (!src->loaded) return "the source critic has no parameters yet (mjs_critic_load)";
+  if (!(tau > 0.0 && tau <= 1.0)) return "tau must lie in (0, 1]";
+  if (!dst->loaded && tau != 1.0) return "a critic that was never loaded takes tau == 1 only (there is nothing to blend with yet)";
+  return "";
+}
+
 int mjs_critic_blend(mjs_critic* dst, const mjs_critic* src, double tau, void* stream) {
-  const auto refuse = [](const std::string& why) { return fail(nullptr, MJS_ERR_INVALID_ARG, "mjs_critic_blend: " + why); };
-  if (!dst || !src) return refuse("null critic");
-  if (!same_shape(dst, src)) return refuse("the two critics differ in shape");
-  if (dst->desc.device != src->desc.device) return refuse("the two critics live on different devices");
-  if (!src->loaded) return refuse("the source critic has no parameters yet (mjs_critic_load)");
-  if (!(tau > 0.0 && tau <= 1.0)) return refuse("tau must lie in (0, 1]");
-  if (!dst->loaded && tau != 1.0) return refuse("a critic that was never loaded takes tau == 1 only (there is nothing to blend with yet)");
+  if (std::string why = blend_refusal(dst, src, tau); !why.empty()) return fail(nullptr, MJS_ERR_INVALID_ARG, "mjs_critic_blend: " + why);
   if (dst == src) return MJS_OK;  // a blend of a copy with itself
   DeviceGuard dev_(dst->desc.device);
   HIP_TRY(nullptr, dev_.err);
@@ -1896,6 +1907,106 @@ int mjs_actor_export(const mjs_actor* a, const mjs_actor_weights* out, void* str
   HIP_TRY(nullptr, dev_.err);
   const crit::Packed P = actor_packed_of(a);
   launch_actor_unpack(a, P.seg, out, (hipStream_t)stream);
+  HIP_TRY(nullptr, hipGetLastError());
+  return MJS_OK;
+}
+
+// ---- the gradient loop (mjs_sac_train.h) ----------------------------------------------------------------------------------------
+// what mjs_sac_draw_batch and mjs_sac_train refuse about the storage and the batch buffers alike; "" = fine
+static std::string draw_refusal(const mjs_replay_storage* st, const mjs_sac_batch* out, int32_t B) {
+  if (std::string why = replay_storage_refusal(st); !why.empty()) return why;
+  if (st->n_cameras > 0) return "the storage holds cameras: the SAC update is state-only (visual critics are not built)";
+  if (!out) return "the batch (mjs_sac_batch) is null";
+  if (out->struct_size != sizeof(mjs_sac_batch)) return "mjs_sac_batch.struct_size does not match this library's header";
+  if (B < 0) return "B is negative";
+  if (B > 0) {
+    if (!out->idx_out || !out->actions || !out->rewards || !out->dones) return "the batch's idx_out, actions, rewards or dones is null";
+    if (st->obs_dim > 0 && (!out->obs || !out->next_obs)) return "the batch's obs or next_obs is null";
+    if (!out->z_next || !out->z_pi) return "the batch's z_next or z_pi is null";
+  }
+  return "";
+}
+static void launch_draw(const mjs_replay_storage* st, const mjs_sac_batch* out, int32_t B, uint64_t seed, uint64_t step, hipStream_t s) {
+  sac::DrawParams p{};
+  p.B = B; p.D = st->obs_dim; p.A = st->action_dim; p.capacity = st->capacity;
+  p.cursor = reinterpret_cast<const unsigned long long*>(st->cursor_dev);
+  p.key0 = (uint32_t)(seed & 0xffffffffu); p.key1 = (uint32_t)(seed >> 32);
+  p.step_lo = (uint32_t)(step & 0xffffffffu); p.step_hi = (uint32_t)(step >> 32);
+  p.s_obs = st->obs; p.s_next_obs = st->next_obs; p.s_actions = st->actions; p.s_rewards = st->rewards; p.s_dones = st->dones;
+  p.idx_out = out->idx_out; p.draws_out = out->draws_out;
+  p.obs = out->obs; p.next_obs = out->next_obs; p.actions = out->actions; p.rewards = out->rewards; p.dones = out->dones;
+  p.z_next = out->z_next; p.z_pi = out->z_pi;
+  sac::draw_batch_kernel<<<dim3((unsigned)(((int64_t)B + sac::DRAW_ROWS - 1) / sac::DRAW_ROWS)), sac::THREADS, 0, s>>>(p);
+}
+
+int mjs_sac_draw_batch(const mjs_replay_storage* st, const mjs_sac_batch* out, int32_t B, uint64_t seed, uint64_t step, void* stream) {
+  if (std::string why = draw_refusal(st, out, B); !why.empty()) return fail(nullptr, MJS_ERR_INVALID_ARG, "mjs_sac_draw_batch: " + why);
+  if (B == 0) return MJS_OK;
+  if (int rc = device_refusal("mjs_sac_draw_batch", st->device)) return rc;
+  DeviceGuard dev_(st->device);
+  HIP_TRY(nullptr, dev_.err);
+  launch_draw(st, out, B, seed, step, (hipStream_t)stream);
+  HIP_TRY(nullptr, hipGetLastError());
+  return MJS_OK;
+}
+
+int mjs_sac_train(const mjs_sac_train_args* a, void* stream) {
+  const auto refuse = [](const std::string& why) { return fail(nullptr, MJS_ERR_INVALID_ARG, "mjs_sac_train: " + why); };
+  if (!a) return refuse("args is null");
+  if (a->struct_size != sizeof(mjs_sac_train_args)) return refuse("mjs_sac_train_args.struct_size does not match this library's header");
+  if (!a->storage || !a->actor || !a->critic || !a->target_critic || !a->critic_opt || !a->actor_opt || !a->batch || !a->target_dev)
+    return refuse("storage, actor, critic, target_critic, critic_opt, actor_opt, batch or target_dev is null");
+  if (a->B < 1) return refuse("B must be at least 1");
+  if (a->G < 0) return refuse("G is negative");
+  if (a->target_update_interval < 1) return refuse("target_update_interval must be at least 1");
+  if (std::string why = draw_refusal(a->storage, a->batch, a->B); !why.empty()) return refuse(why);
+  const mjs_replay_storage* st = a->storage;
+  if (st->obs_dim != a->actor->desc.in_dim || st->obs_dim != a->critic->desc.obs_dim) return refuse("the storage's obs_dim is not the networks'");
+  if (st->action_dim != a->actor->desc.action_dim || st->action_dim != a->critic->desc.action_dim) return refuse("the storage's action_dim is not the networks'");
+  if (st->device != a->actor->desc.device || st->device != a->critic->desc.device || st->device != a->target_critic->desc.device)
+    return refuse("the storage, the actor and the critics live on different devices");
+  if (a->critic_opt->critic != a->critic) return refuse("critic_opt was created for another critic");
+  if (a->actor_opt->actor != a->actor) return refuse("actor_opt was created for another actor");
+  if (a->target_critic == a->critic) return refuse("target_critic and critic are one object");
+  if (!(a->tau > 0.0 && a->tau <= 1.0)) return refuse("tau must lie in (0, 1]");
+  if (!(a->gamma >= 0.0 && a->gamma <= 1.0)) return refuse("gamma must lie in [0, 1]");
+  if (!(a->critic_lr >= 0.0) || !std::isfinite(a->critic_lr) || !(a->actor_lr >= 0.0) || !std::isfinite(a->actor_lr))
+    return refuse("critic_lr and actor_lr must be finite and >= 0");
+  // the three steps' arguments over the scratch batch, and what their entry points and the blend refuse, before the first launch
+  const mjs_sac_batch* bt = a->batch;
+  const float* ent_dev = a->ent_coef_dev ? a->ent_coef_dev : a->entropy ? a->entropy->ent_coef_dev : nullptr;
+  mjs_td_target_args td{};
+  td.struct_size = sizeof(td); td.B = a->B;
+  td.next_obs_dev = bt->next_obs; td.rewards_dev = bt->rewards; td.dones_dev = bt->dones; td.z_dev = bt->z_next;
+  td.gamma = a->gamma; td.ent_coef = a->ent_coef; td.ent_coef_dev = ent_dev; td.target_out_dev = a->target_dev;
+  mjs_critic_grad_args cg{};
+  cg.struct_size = sizeof(cg); cg.B = a->B;
+  cg.obs_dev = bt->obs; cg.actions_dev = bt->actions; cg.target_dev = a->target_dev;
+  mjs_entropy_step ent{};
+  if (a->entropy) ent = *a->entropy;
+  mjs_actor_grad_args ag{};
+  ag.struct_size = sizeof(ag); ag.B = a->B;
+  ag.obs_dev = bt->obs; ag.z_dev = bt->z_pi; ag.critic = a->critic; ag.ent_coef = a->ent_coef; ag.ent_coef_dev = ent_dev;
+  ag.entropy = a->entropy ? &ent : nullptr;
+  if (std::string why = td_refusal(a->actor, a->target_critic, &td); !why.empty()) return refuse("mjs_sac_td_target: " + why);
+  if (std::string why = grad_refusal(a->critic, a->critic_opt, &cg); !why.empty()) return refuse("mjs_critic_update: " + why);
+  if (std::string why = actor_grad_refusal(a->actor, a->actor_opt, &ag); !why.empty()) return refuse("mjs_actor_update: " + why);
+  if (std::string why = blend_refusal(a->target_critic, a->critic, a->tau); !why.empty()) return refuse("mjs_critic_blend: " + why);
+  if (a->G == 0) return MJS_OK;
+  if (int rc = device_refusal("mjs_sac_train", st->device)) return rc;
+  DeviceGuard dev_(st->device);
+  HIP_TRY(nullptr, dev_.err);
+  const int64_t t0 = ent.t;
+  for (int32_t g = 0; g < a->G; g++) {
+    const uint64_t step = a->step0 + (uint64_t)g;
+    launch_draw(st, bt, a->B, a->seed, step, (hipStream_t)stream);
+    if (int rc = mjs_sac_td_target(a->actor, a->target_critic, &td, stream)) return rc;
+    if (int rc = mjs_critic_update(a->critic_opt, &cg, a->critic_lr, stream)) return rc;
+    ent.t = t0 + g;
+    if (int rc = mjs_actor_update(a->actor_opt, &ag, a->actor_lr, stream)) return rc;
+    if ((step + 1) % (uint64_t)a->target_update_interval == 0)
+      if (int rc = mjs_critic_blend(a->target_critic, a->critic, a->tau, stream)) return rc;
+  }
   HIP_TRY(nullptr, hipGetLastError());
   return MJS_OK;
 }
