@@ -66,8 +66,19 @@ __device__ __forceinline__ bool pending_is_due(const KernelParams& p, uint8_t fl
     __builtin_amdgcn_sched_barrier(0);                                                      \
     if ((p).stamps && threadIdx.x == 0) (p).stamps[(size_t)blockIdx.x * 16 + (slot)] = t_; \
   } while (0)
+// Robot-Reach's role loop, both dynamics wavefronts (lane 0 of each): slots (role) * 8 + k of a second slot block per workgroup,
+// behind the first blocks of all workgroups (needs N >= 64: 16 N slots hold 2 x N / 64 blocks).
+#define MJS_ROLE_STAMP(p, role, k)                                                                                         \
+  do {                                                                                                                     \
+    unsigned long long t_;                                                                                                 \
+    __builtin_amdgcn_sched_barrier(0);                                                                                     \
+    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");                                             \
+    __builtin_amdgcn_sched_barrier(0);                                                                                     \
+    if ((p).stamps && (p).N >= 64 && (threadIdx.x & 63) == 0) (p).stamps[((size_t)gridDim.x + blockIdx.x) * 16 + (role) * 8 + (k)] = t_; \
+  } while (0)
 #else
 #define MJS_STAMP(p, slot) do { } while (0)
+#define MJS_ROLE_STAMP(p, role, k) do { } while (0)
 #endif
 
 template <int OBS>

@@ -1505,6 +1505,188 @@ MJS_DEV bool hand_over_bad(int* bad_x, int lane, int role, bool bad, const doubl
 #define MJS_MASK_STATS(p, mask, before) do { } while (0)
 #endif
 
+// ------------------------------------------------------------------------------------------------------------------
+// The role loop of the two dynamics wavefronts (rr::kernel3 substeps 1-19, rr::kernel<false, 2> substeps 0-19), one shape
+// for both kernels. Per substep: each role's own block -> barrier 1 (qfrc_smooth published) -> role 0 solves while role 1
+// waits -> barrier 2 (qacc published) -> both integrate, same bits.
+//
+// The loop is ROTATED: an iteration is the integration of the PREVIOUS substep's qacc and then the role's own block, one
+// scheduling region up to barrier 1, so the integration's dependency stalls (6.9 cycles per instruction when it stood alone
+// behind barrier 2, between the role branch, the per-lane fallback branch and the latch) fill with the block's work. The
+// first block is peeled and each role has its own loop (the role test is outside), followed by its own copy of the last
+// integration: with one shared copy behind the join of the two loops the register allocator moves about 50 registers
+// through AGPRs in every iteration of role 1's loop (+1.6 us per launch, profiles/reach_tail_ab.txt). The dq2 > 0.01
+// fallback (exact sincos) leaves the region by a wave-uniform test BEHIND the block: a cold copy evaluates the exact
+// functions and the block again and keeps the results of the lanes that needed them, which is per lane what a loop that
+// integrates behind barrier 2 does.
+//
+// Who owns cs[0] / sn[0] (cos / sin of the BASE joint's angle): BOTH wavefronts carry the pair through every substep like the
+// other five, although the generated dynamics never read it (M and the bias of this arm do not depend on the base joint's
+// angle; its consumers are fk_cs / store_cs in the epilogue and the solo tail). Leaving the pair to role 1 alone, rotated
+// one substep late between the barriers and handed to role 0 after the loop, was measured and is slower (same profile).
+
+// semi-implicit Euler from a substep's qacc, cos / sin by rotate_small; returns sum(dq^2) for the fallback test
+MJS_DEV double integrate_role(State& st, double* cs, double* sn, const double* qacc) {
+  double dq2 = 0;
+#pragma unroll
+  for (int j = 0; j < NJ; j++) {
+    st.v[j] += MJS_RR_PHYSICS_DT * qacc[j];
+    double dq = MJS_RR_PHYSICS_DT * st.v[j];
+    st.q[j] += dq;
+    dq2 = fma(dq, dq, dq2);
+    rotate_small(cs[j], sn[j], dq);
+  }
+  st.time += MJS_RR_PHYSICS_DT;
+  return dq2;
+}
+// the fallback of one lane (some |dq| may exceed 0.1 rad, runaway state): the exact functions
+MJS_DEV void exact_cs(const State& st, double* cs, double* sn) {
+#pragma unroll
+  for (int j = 0; j < NJ; j++) sincos(st.q[j], &sn[j], &cs[j]);
+}
+// role 1's own block: servo set-point, actuator forces and bias forces -> qfrc_smooth
+MJS_DEV void role1_block(const State& st, const double* cs, const double* sn, const double* q0, const double* q1, double t0, double t1,
+                         double inv_span, double* qfrc) {
+  double t = fmin(fmax(st.time, t0), t1);
+  double ctrl[NJ], bias[NJ], fact[NJ];
+#pragma unroll
+  for (int j = 0; j < NJ; j++) ctrl[j] = q0[j] + (q1[j] - q0[j]) * (t - t0) * inv_span;
+  actuator_forces(st.q, st.v, ctrl, fact);
+  ur5e_bias_gen(cs, sn, st.v, bias);
+#pragma unroll
+  for (int j = 0; j < NJ; j++) qfrc[j] = fact[j] - bias[j];  // qfrc_smooth = -bias + actuator
+}
+// role 0's own block: joint-space inertia, implicitfast matrix, U D U^T and U^-1 (W strictly lower, Dinv); of the actuators
+// only the clamp mask. GENERATED: M(q) + armature + dt kd -> U D U^T -> U^-1 as ONE generated, list-scheduled block
+// (tools/gen_ur5e_dynamics.py factor_inverse: the pivot chain runs next to the tail of the CRBA by construction; profiles/r04_g_*)
+template <bool GENERATED>
+MJS_DEV int role0_block(const State& st, const double* cs, const double* sn, const double* q0, const double* dq01, double t0, double t1,
+                        double inv_span, bool ctrl_inside, double W[NJ][NJ], double* Dinv) {
+  double t = fmin(fmax(st.time, t0), t1);
+  const int clamped = actuator_clamp_mask(st.q, st.v, q0, dq01, t - t0, inv_span, ctrl_inside);
+  if constexpr (GENERATED) {
+    double dd[NJ], Wp[15];
+#pragma unroll
+    for (int j = 0; j < NJ; j++) dd[j] = MJS_UR_ARMATURE + (((clamped >> j) & 1) ? 0.0 : MJS_RR_PHYSICS_DT * MJS_UR_ACT_KD[j]);
+    ur5e_MW_gen(cs, sn, dd, Wp, Dinv);
+#pragma unroll
+    for (int r = 1; r < NJ; r++) {
+#pragma unroll
+      for (int j = 0; j < r; j++) W[r][j] = Wp[r * (r - 1) / 2 + j];
+    }
+  } else {
+    double M[21], A[NJ][NJ];
+    ur5e_M_gen(cs, sn, M);
+#pragma unroll
+    for (int r = 0; r < NJ; r++) {
+#pragma unroll
+      for (int j = 0; j <= r; j++) A[r][j] = M[r * (r + 1) / 2 + j];
+    }
+    factor_system(A, clamped, Dinv);
+    invert_unit_upper(A, W);
+  }
+  return clamped;
+}
+
+// Returns mj_checkAcc's verdict; both wavefronts leave with the same st, cs, sn. Stamps (diagnostic build): role 0's 8-12 as
+// before, with 8 at the top of iteration 10 (ahead of the integration, which now belongs to the block) and 12 next to 11;
+// MJS_ROLE_STAMP 0-3 on both roles behind barrier 2 of substep 10, 4 at the top of iteration 11.
+template <bool GENERATED, int FIRST>
+MJS_DEV bool role_loop(const KernelParams& p, double (*xch)[64], int* bad_x, int lane, int role, State& st, double* cs, double* sn,
+                       const double* q0, const double* q1, double t0, double t1, double inv_span, bool bad, [[maybe_unused]] int& mask_before) {
+  double dq01[NJ];  // the set-point lerp's loop-invariant difference (role 0's actuator_clamp_mask)
+#pragma unroll
+  for (int j = 0; j < NJ; j++) dq01[j] = q1[j] - q0[j];
+  const bool ctrl_inside = servo_span_inside_ctrlrange(q0, q1);
+  double qacc[NJ] = {0, 0, 0, 0, 0, 0};  // lives across substeps on role 1: it checks a substep's qacc during the next one's wait
+  // role 1 from its finished block to the qacc of the substep
+  auto role1_exchange = [&](const double* qfrc) {
+#pragma unroll
+    for (int j = 0; j < NJ; j++) xch[j][lane] = qfrc[j];
+    __syncthreads();  // qfrc_smooth published
+    bad = qacc_is_bad_while_waiting(qacc) || bad;  // the previous substep's
+    __syncthreads();  // qacc published
+#pragma unroll
+    for (int j = 0; j < NJ; j++) qacc[j] = xch[6 + j][lane];
+  };
+  // role 0 likewise; opaque register uses pin the whole factorisation before the barrier
+  auto role0_exchange = [&](double W[NJ][NJ], double* Dinv, bool stamps) {
+    double rhs[NJ];
+#pragma unroll
+    for (int r = 0; r < NJ; r++) {
+      asm volatile("" : "+v"(Dinv[r]));
+#pragma unroll
+      for (int j = 0; j < r; j++) asm volatile("" : "+v"(W[r][j]));
+    }
+    if (stamps) MJS_STAMP(p, 9);
+    __syncthreads();  // qfrc_smooth published
+    if (stamps) MJS_STAMP(p, 10);
+#pragma unroll
+    for (int j = 0; j < NJ; j++) rhs[j] = xch[j][lane];
+    apply_inverse(W, Dinv, rhs, qacc);
+#pragma unroll
+    for (int j = 0; j < NJ; j++) xch[6 + j][lane] = qacc[j];
+    __syncthreads();  // qacc published
+    if (stamps) MJS_STAMP(p, 11);
+  };
+  // the last substep's integration, with the per-lane fallback in place (one copy per role, see above)
+  auto integrate_with_fallback = [&]() {
+    if (!(integrate_role(st, cs, sn, qacc) <= 0.01)) exact_cs(st, cs, sn);
+  };
+  if (role == 1) {
+    double qfrc[NJ];
+    role1_block(st, cs, sn, q0, q1, t0, t1, inv_span, qfrc);
+    role1_exchange(qfrc);
+#pragma unroll 1
+    for (int s = FIRST + 1; s < MJS_RR_NSUB; s++) {
+      if (s == 11) MJS_ROLE_STAMP(p, 1, 4);
+      const double dq2 = integrate_role(st, cs, sn, qacc);
+      role1_block(st, cs, sn, q0, q1, t0, t1, inv_span, qfrc);
+      const bool exact = !(dq2 <= 0.01);
+      if (__builtin_expect(__any(exact), 0)) {  // cold: per lane what a loop that integrates behind barrier 2 does
+        double again[NJ];
+        if (exact) exact_cs(st, cs, sn);
+        role1_block(st, cs, sn, q0, q1, t0, t1, inv_span, again);
+#pragma unroll
+        for (int j = 0; j < NJ; j++) qfrc[j] = exact ? again[j] : qfrc[j];
+      }
+      role1_exchange(qfrc);
+      if (s == 10) { MJS_ROLE_STAMP(p, 1, 0); MJS_ROLE_STAMP(p, 1, 1); MJS_ROLE_STAMP(p, 1, 2); MJS_ROLE_STAMP(p, 1, 3); }
+    }
+    integrate_with_fallback();
+  } else {
+    double W[NJ][NJ], Dinv[NJ];
+    int clamped = role0_block<GENERATED>(st, cs, sn, q0, dq01, t0, t1, inv_span, ctrl_inside, W, Dinv);
+    MJS_MASK_STATS(p, clamped, mask_before);
+    role0_exchange(W, Dinv, false);
+#pragma unroll 1
+    for (int s = FIRST + 1; s < MJS_RR_NSUB; s++) {
+      if (s == 10) MJS_STAMP(p, 8);
+      if (s == 11) MJS_ROLE_STAMP(p, 0, 4);
+      const double dq2 = integrate_role(st, cs, sn, qacc);
+      clamped = role0_block<GENERATED>(st, cs, sn, q0, dq01, t0, t1, inv_span, ctrl_inside, W, Dinv);
+      const bool exact = !(dq2 <= 0.01);
+      if (__builtin_expect(__any(exact), 0)) {  // cold, as on role 1
+        double W2[NJ][NJ], Dinv2[NJ];
+        if (exact) exact_cs(st, cs, sn);
+        const int clamped2 = role0_block<GENERATED>(st, cs, sn, q0, dq01, t0, t1, inv_span, ctrl_inside, W2, Dinv2);
+        clamped = exact ? clamped2 : clamped;
+#pragma unroll
+        for (int r = 0; r < NJ; r++) {
+          Dinv[r] = exact ? Dinv2[r] : Dinv[r];
+#pragma unroll
+          for (int j = 0; j < r; j++) W[r][j] = exact ? W2[r][j] : W[r][j];
+        }
+      }
+      MJS_MASK_STATS(p, clamped, mask_before);
+      role0_exchange(W, Dinv, s == 10);
+      if (s == 10) { MJS_STAMP(p, 12); MJS_ROLE_STAMP(p, 0, 0); MJS_ROLE_STAMP(p, 0, 1); MJS_ROLE_STAMP(p, 0, 2); MJS_ROLE_STAMP(p, 0, 3); }
+    }
+    integrate_with_fallback();
+  }
+  return hand_over_bad(bad_x, lane, role, bad, qacc);
+}
+
 // ROLES == 1: one wavefront steps 64 envs. ROLES == 2 (default for stepping): two wavefronts of
 // one workgroup, placed on different SIMDs of the CU, step the same 64 envs: role 0 builds M(q),
 // factorises the implicitfast matrix (U D U^T) and inverts U while role 1 evaluates the servo
@@ -1560,79 +1742,8 @@ __global__ __launch_bounds__(64 * ROLES) void kernel(KernelParams p) {
     if (role != 0) return;
     MJS_RR_SOLO_TAIL(0, true);
   } else if constexpr (ROLES == 2) {
-    double dq01[NJ];  // the set-point lerp's loop-invariant difference (role 0's actuator_clamp_mask)
-#pragma unroll
-    for (int j = 0; j < NJ; j++) dq01[j] = q1[j] - q0[j];
-    const bool ctrl_inside = servo_span_inside_ctrlrange(q0, q1);
-    double qacc[NJ] = {0, 0, 0, 0, 0, 0};  // lives across substeps on role 1: it checks a substep's qacc during the next one's wait
-#pragma unroll 1
-    for (int s = 0; s < MJS_RR_NSUB; s++) {
-      if (role == 1) {
-        // role 1: servo set-point, actuator forces and bias forces -> qfrc_smooth
-        double t = fmin(fmax(st.time, t0), t1);
-        double ctrl[NJ], bias[NJ], fact[NJ];
-#pragma unroll
-        for (int j = 0; j < NJ; j++) ctrl[j] = q0[j] + (q1[j] - q0[j]) * (t - t0) * inv_span;
-        actuator_forces(st.q, st.v, ctrl, fact);
-        ur5e_bias_gen(cs, sn, st.v, bias);
-#pragma unroll
-        for (int j = 0; j < NJ; j++) xch[0][j][lane] = fact[j] - bias[j];  // qfrc_smooth = -bias + actuator
-        __syncthreads();  // qfrc_smooth published
-        bad = qacc_is_bad_while_waiting(qacc) || bad;  // the previous substep's
-        __syncthreads();  // qacc published
-#pragma unroll
-        for (int j = 0; j < NJ; j++) qacc[j] = xch[0][6 + j][lane];
-      } else {
-        // role 0: joint-space inertia, implicitfast matrix, U D U^T and U^-1, all before the barrier
-        // (overlapping role 1); only the clamp mask of the actuators is recomputed here
-        if (s == 10) MJS_STAMP(p, 8);
-        double t = fmin(fmax(st.time, t0), t1);
-        double M[21], A[NJ][NJ], W[NJ][NJ], Dinv[NJ], rhs[NJ];
-        int clamped = actuator_clamp_mask(st.q, st.v, q0, dq01, t - t0, inv_span, ctrl_inside);
-        ur5e_M_gen(cs, sn, M);
-#pragma unroll
-        for (int r = 0; r < NJ; r++) {
-#pragma unroll
-          for (int j = 0; j <= r; j++) A[r][j] = M[r * (r + 1) / 2 + j];
-        }
-        factor_system(A, clamped, Dinv);
-        invert_unit_upper(A, W);
-        // opaque register uses pin the whole factorisation before the barrier
-#pragma unroll
-        for (int r = 0; r < NJ; r++) {
-          asm volatile("" : "+v"(Dinv[r]));
-#pragma unroll
-          for (int j = 0; j < r; j++) asm volatile("" : "+v"(W[r][j]));
-        }
-        if (s == 10) MJS_STAMP(p, 9);
-        __syncthreads();  // qfrc_smooth published
-        if (s == 10) MJS_STAMP(p, 10);
-#pragma unroll
-        for (int j = 0; j < NJ; j++) rhs[j] = xch[0][j][lane];
-        apply_inverse(W, Dinv, rhs, qacc);
-#pragma unroll
-        for (int j = 0; j < NJ; j++) xch[0][6 + j][lane] = qacc[j];
-        __syncthreads();  // qacc published
-        if (s == 10) MJS_STAMP(p, 11);
-      }
-      // integration on both wavefronts (same bits); mj_checkAcc is role 1's alone (above), handed over after the loop
-      double dq2 = 0;
-#pragma unroll
-      for (int j = 0; j < NJ; j++) {
-        st.v[j] += MJS_RR_PHYSICS_DT * qacc[j];
-        double dq = MJS_RR_PHYSICS_DT * st.v[j];
-        st.q[j] += dq;
-        dq2 = fma(dq, dq, dq2);
-        rotate_small(cs[j], sn[j], dq);
-      }
-      if (!(dq2 <= 0.01)) {  // some |dq| may exceed 0.1 rad (runaway state): fall back to the exact functions
-#pragma unroll
-        for (int j = 0; j < NJ; j++) sincos(st.q[j], &sn[j], &cs[j]);
-      }
-      st.time += MJS_RR_PHYSICS_DT;
-      if (role == 0 && s == 10) MJS_STAMP(p, 12);
-    }
-    bad = hand_over_bad(bad_x, lane, role, bad, qacc);
+    [[maybe_unused]] int mask_before = 0;
+    bad = role_loop<false, 0>(p, xch[0], bad_x, lane, role, st, cs, sn, q0, q1, t0, t1, inv_span, bad, mask_before);
   }
   // epilogue on both wavefronts (they hold the same numbers): role 1 writes the 25 state rows the step changed while role 0
   // works out observables, reward, flags and outputs. Not with the same-step auto-reset: role 0 may then rewrite the state rows
@@ -1811,93 +1922,12 @@ __global__ __launch_bounds__(192) void kernel3(KernelParams p) {
       if (role != 0) return;
       MJS_RR_SOLO_TAIL(1, false);  // no warm start across the hand-over: the first robust substep has no rows (guard), later ones start from it
     } else {
-      double dq01[NJ];  // the set-point lerp's loop-invariant difference (role 0's actuator_clamp_mask)
-#pragma unroll
-      for (int j = 0; j < NJ; j++) dq01[j] = q1[j] - q0[j];
-      const bool ctrl_inside = servo_span_inside_ctrlrange(q0, q1);
-      double qacc[NJ] = {0, 0, 0, 0, 0, 0};  // lives across substeps on role 1: it checks a substep's qacc during the next one's wait
-#pragma unroll 1
-      for (int s = 1; s < MJS_RR_NSUB; s++) {
-        if (role == 1) {
-          double t = fmin(fmax(st.time, t0), t1);
-          double ctrl[NJ], bias[NJ], fact[NJ];
-#pragma unroll
-          for (int j = 0; j < NJ; j++) ctrl[j] = q0[j] + (q1[j] - q0[j]) * (t - t0) * inv_span;
-          actuator_forces(st.q, st.v, ctrl, fact);
-          ur5e_bias_gen(cs, sn, st.v, bias);
-#pragma unroll
-          for (int j = 0; j < NJ; j++) xch[j][lane] = fact[j] - bias[j];  // qfrc_smooth = -bias + actuator
-          __syncthreads();  // qfrc_smooth published
-          bad = qacc_is_bad_while_waiting(qacc) || bad;  // the previous substep's
-          __syncthreads();  // qacc published
-#pragma unroll
-          for (int j = 0; j < NJ; j++) qacc[j] = xch[6 + j][lane];
-        } else {
-          if (s == 10) MJS_STAMP(p, 8);
-          double t = fmin(fmax(st.time, t0), t1);
-          double M[21], A[NJ][NJ], W[NJ][NJ], Dinv[NJ], rhs[NJ];
-          int clamped = actuator_clamp_mask(st.q, st.v, q0, dq01, t - t0, inv_span, ctrl_inside);
-          MJS_MASK_STATS(p, clamped, mask_before);
 #ifndef MJS_RR_SPLIT_FACTOR
-          // M(q) + armature + dt kd -> U D U^T -> U^-1 as ONE generated, list-scheduled block (tools/gen_ur5e_dynamics.py factor_inverse:
-          // the pivot chain runs next to the tail of the CRBA by construction; profiles/r04_g_*)
-          {
-            double dd[NJ], Wp[15];
-#pragma unroll
-            for (int j = 0; j < NJ; j++) dd[j] = MJS_UR_ARMATURE + (((clamped >> j) & 1) ? 0.0 : MJS_RR_PHYSICS_DT * MJS_UR_ACT_KD[j]);
-            ur5e_MW_gen(cs, sn, dd, Wp, Dinv);
-#pragma unroll
-            for (int r = 1; r < NJ; r++) {
-#pragma unroll
-              for (int j = 0; j < r; j++) W[r][j] = Wp[r * (r - 1) / 2 + j];
-            }
-            (void)M; (void)A;
-          }
+      constexpr bool generated_block = true;
 #else
-          ur5e_M_gen(cs, sn, M);
-#pragma unroll
-          for (int r = 0; r < NJ; r++) {
-#pragma unroll
-            for (int j = 0; j <= r; j++) A[r][j] = M[r * (r + 1) / 2 + j];
-          }
-          factor_system(A, clamped, Dinv);
-          invert_unit_upper(A, W);
+      constexpr bool generated_block = false;
 #endif
-#pragma unroll
-          for (int r = 0; r < NJ; r++) {
-            asm volatile("" : "+v"(Dinv[r]));
-#pragma unroll
-            for (int j = 0; j < r; j++) asm volatile("" : "+v"(W[r][j]));
-          }
-          if (s == 10) MJS_STAMP(p, 9);
-          __syncthreads();  // qfrc_smooth published
-          if (s == 10) MJS_STAMP(p, 10);
-#pragma unroll
-          for (int j = 0; j < NJ; j++) rhs[j] = xch[j][lane];
-          apply_inverse(W, Dinv, rhs, qacc);
-#pragma unroll
-          for (int j = 0; j < NJ; j++) xch[6 + j][lane] = qacc[j];
-          __syncthreads();  // qacc published
-          if (s == 10) MJS_STAMP(p, 11);
-        }
-        // integration on both wavefronts (same bits); mj_checkAcc is role 1's alone (above), handed over after the loop
-        double dq2 = 0;
-#pragma unroll
-        for (int j = 0; j < NJ; j++) {
-          st.v[j] += MJS_RR_PHYSICS_DT * qacc[j];
-          double dq = MJS_RR_PHYSICS_DT * st.v[j];
-          st.q[j] += dq;
-          dq2 = fma(dq, dq, dq2);
-          rotate_small(cs[j], sn[j], dq);
-        }
-        if (!(dq2 <= 0.01)) {
-#pragma unroll
-          for (int j = 0; j < NJ; j++) sincos(st.q[j], &sn[j], &cs[j]);
-        }
-        st.time += MJS_RR_PHYSICS_DT;
-        if (role == 0 && s == 10) MJS_STAMP(p, 12);
-      }
-      bad = hand_over_bad(bad_x, lane, role, bad, qacc);
+      bad = role_loop<generated_block, 1>(p, xch, bad_x, lane, role, st, cs, sn, q0, q1, t0, t1, inv_span, bad, mask_before);
       // epilogue on both wavefronts (same numbers): role 1 writes the 25 state rows the step changed while role 0 works out
       // observables, reward, flags and outputs (not with the same-step auto-reset: role 0 may then rewrite those rows)
       if (role == 1) {

@@ -37,6 +37,17 @@ inline void mjs_stamps_report(const unsigned long long* stamps_dev, int num_envs
   for (int w = 0; w < W; w++) own += (double)(host[16 * w + 6] - host[16 * w + 0]) / W;
   std::fprintf(stderr, "[MJS_STAMPS] cycles: load+IK %.0f (of which wave 0's own load + sincos + substep 0: %.0f) | substeps %.0f | fk+obs %.0f | contacts %.0f | store %.0f\n", d[0], own, d[1], d[2], d[3], d[4]);
   std::fprintf(stderr, "[MJS_STAMPS] role-0 substep 10: CRBA+factor+invert %.0f | barrier %.0f | apply inverse+publish+barrier %.0f | integrate %.0f\n", e[0], e[1], e[2], e[3]);
+  if (task == MJS_TASK_ROBOT_REACH && num_envs >= 64) {  // MJS_ROLE_STAMP (mjs_reach.h): substep 10's tail on both dynamics wavefronts
+    for (int role = 0; role < 2; role++) {
+      double t[4] = {0, 0, 0, 0};
+      for (int w = 0; w < W; w++) {
+        const unsigned long long* s = host + 16 * (size_t)(W + w) + 8 * role;
+        for (int k = 0; k < 4; k++) t[k] += (double)(s[k + 1] - s[k]) / W;
+      }
+      std::fprintf(stderr, "[MJS_STAMPS] role-%d substep 10 after barrier 2: qacc read %.0f | v, q, dq2 %.0f | rotate_small %.0f | fallback test + latch, to the top of substep 11 %.0f\n",
+                   role, t[0], t[1], t[2], t[3]);
+    }
+  }
   if (task == MJS_TASK_ROBOT_REACH) {  // MJS_MASK_STATS (mjs_reach.h): counters summed over every launch of the handle
     double n = 0, changed = 0, nonzero = 0, lanes = 0;
     for (int w = 0; w < W; w++) { n += (double)host[16 * w + 13]; changed += (double)host[16 * w + 14]; nonzero += (double)host[16 * w + 15]; lanes += (double)host[16 * w + 7]; }
