@@ -770,6 +770,75 @@ typedef struct {
  * launch. G == 0 does nothing and returns 0. */
 int mjs_sac_train(const mjs_sac_train_args* args, void* stream);
 
+/* Episode statistics on the device (csrc/mjs_monitor.h; entry points added after abi 3 as well): the [T, N] blocks the rollouts above
+ * write, reduced to finished episodes. A restatement of SB3's Monitor + ep_info_buffer (stable_baselines3/common/monitor.py, a
+ * deque(maxlen=100); scripts/sb3/reach_sac.py:83) and of evaluate_policy's per-env episode targets. The entry points are stateless: the
+ * state is a descriptor of caller-owned device memory.
+ *
+ * Row (t, n) of a block counts iff step_type[t, n] != MJS_STEP_FIRST under MJS_AUTORESET_NEXT_STEP and always under
+ * MJS_AUTORESET_SAME_STEP (mjs_replay_add's rule for a transition). A counting row does ep_return[n] += reward[t, n] in float64, one add
+ * per row in t order, and ep_length[n] += 1. Where terminated | truncated on a counting row the episode ends: if quota == NULL or
+ * ep_count[n] < quota[n] it is RECORDED (return, length, success = is_success[t, n], terminated = terminated[t, n], env = n) and
+ * ep_count[n] += 1; in every case both accumulators return to 0. The recorded episodes of a block are ordered by (t, n); the e-th goes
+ * to ring slot (count + e) % window, count = *cursor_dev = the number of episodes ever recorded, and afterwards count += E. Of a block
+ * with E > window episodes only the last `window` are written. A negative quota entry cannot be checked without reading the device: its
+ * effect is undefined. Returns are kept in full float64 (Monitor rounds them to 6 digits; this does not). Neither entry point reads
+ * anything back to the host or synchronises, and two runs from equal state give equal bits. */
+typedef struct {
+  uint32_t struct_size;      /* sizeof(mjs_monitor_state), validated like mjs_config's */
+  int32_t device;            /* HIP device ordinal */
+  int32_t num_envs;          /* N >= 1 */
+  int32_t window;            /* W, ring slots: >= 1 */
+  double* ep_return;         /* [N]: the running episode's return */
+  int32_t* ep_length;        /* [N]: the running episode's counting rows */
+  int64_t* ep_count;         /* [N]: episodes recorded for the env */
+  const int64_t* quota;      /* [N] non-negative, or NULL (unlimited): episodes of an env beyond it are not recorded */
+  uint64_t* cursor_dev;      /* one uint64: episodes ever recorded */
+  double* ring_return;       /* [W] */
+  int32_t* ring_length;      /* [W] */
+  uint8_t* ring_success;     /* [W] */
+  uint8_t* ring_terminated;  /* [W]: 1 = terminated, 0 = truncated */
+  int32_t* ring_env;         /* [W] */
+} mjs_monitor_state;         /* 96 bytes */
+typedef struct {
+  uint32_t struct_size;        /* sizeof(mjs_monitor_block) */
+  int32_t T;                   /* control steps of the block: >= 0 */
+  int32_t N;                   /* envs of the block: the state's num_envs */
+  int32_t autoreset;           /* MJS_AUTORESET_NEXT_STEP or MJS_AUTORESET_SAME_STEP, the mode the block was made under */
+  const double* reward;        /* [T, N] */
+  const uint8_t* terminated;   /* [T, N] */
+  const uint8_t* truncated;    /* [T, N] */
+  const uint8_t* is_success;   /* [T, N] */
+  const uint8_t* step_type;    /* [T, N]: required under next-step auto-reset, ignored otherwise */
+} mjs_monitor_block;           /* 56 bytes */
+/* what mjs_monitor_summary writes: MJS_MONITOR_SUMMARY float64 values over the K = min(count, window) live records. With K == 0 the
+ * count and the three sums are 0 and every other value NaN (SB3's safe_mean of an empty buffer). */
+enum {
+  MJS_MONITOR_COUNT = 0,          /* K */
+  MJS_MONITOR_RETURN_MEAN = 1,    /* RETURN_SUM / K, one rounding */
+  MJS_MONITOR_RETURN_STD = 2,     /* sqrt(sum((x - mean)^2) / K): the population value, numpy.std's definition */
+  MJS_MONITOR_LENGTH_MEAN = 3,    /* LENGTH_SUM / K */
+  MJS_MONITOR_SUCCESS_RATE = 4,   /* SUCCESS_COUNT / K */
+  MJS_MONITOR_RETURN_MIN = 5,
+  MJS_MONITOR_RETURN_MAX = 6,
+  MJS_MONITOR_RETURN_SUM = 7,     /* float64 adds in a fixed order (csrc/mjs_monitor.h) */
+  MJS_MONITOR_LENGTH_SUM = 8,     /* exact (an int64 sum) */
+  MJS_MONITOR_SUCCESS_COUNT = 9,  /* exact */
+  MJS_MONITOR_SUMMARY = 10
+};
+/* bytes of the workspace mjs_monitor_update needs for a block of T x N rows (chunk counts and every row's end record); 0 for a bad
+ * argument */
+uint64_t mjs_monitor_workspace_bytes(int32_t T, int32_t N);
+/* Advances the state over a block: FOUR launches on the caller's stream (walk, count, scan, scatter). workspace_dev:
+ * mjs_monitor_workspace_bytes(T, N) bytes, 16-byte aligned, overwritten. MJS_ERR_INVALID_ARG (nothing launched, text in
+ * mjs_last_error(NULL)) for a null argument or required pointer (every pointer of the state but quota; reward, terminated, truncated and
+ * is_success of the block), a wrong struct_size, num_envs < 1, window < 1, a block whose N is not the state's num_envs, T < 0, T * N >=
+ * 2^31, MJS_AUTORESET_DISABLED (or no mode at all), or next-step auto-reset without step_type. T == 0 does nothing and returns 0. */
+int mjs_monitor_update(const mjs_monitor_state* state, const mjs_monitor_block* block, void* workspace_dev, void* stream);
+/* The ring's live records reduced into out_dev, float64 [MJS_MONITOR_SUMMARY] on the device: ONE launch of one workgroup, sums in a
+ * fixed order. MJS_ERR_INVALID_ARG (nothing launched) for a null argument or a state mjs_monitor_update would refuse. */
+int mjs_monitor_summary(const mjs_monitor_state* state, double* out_dev, void* stream);
+
 /* Replaces the Robot entity's control API on a stand-alone UR5e (entities/robots/robot.py:198-272): Robot.moveJ :211-216,
  * Robot.movej_IK :198-209, Robot.servoL :218-225, Robot.servoJ :227-259, then n_substeps x (Robot.before_substep :261-272 +
  * JointTrajectory.get_target_joint_positions joint_trajectory.py:41-47; Physics.step), then Robot.get_tcp_pose :153-168.

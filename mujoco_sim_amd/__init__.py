@@ -20,6 +20,7 @@ from .environments.tasks.robot_push_button import RobotPushButtonTask
 from .environments.tasks.robot_planar_push import RobotPushConfig, RobotPushTask
 from .policies import (DeviceActor, DeviceActorOptimizer, DeviceCritic, DeviceCriticOptimizer, DeviceEncoder, DeviceEntropyCoef,  # noqa: F401
                        sac_gradient_step, sac_td_target)
+from .monitor import DeviceEpisodeMonitor, evaluate_policy  # noqa: F401
 from .recording import LeRobotDatasetRecorder  # noqa: F401
 from .replay import DeviceReplayBuffer  # noqa: F401
 from .sac import DeviceSAC  # noqa: F401

@@ -56,6 +56,7 @@ EXPORTED_SYMBOLS = [
     "mjs_critic_export",
     "mjs_actor_opt_create", "mjs_actor_opt_destroy", "mjs_actor_train_workspace_bytes", "mjs_actor_grad", "mjs_actor_update", "mjs_actor_export",
     "mjs_sac_draw_batch", "mjs_sac_train",
+    "mjs_monitor_workspace_bytes", "mjs_monitor_update", "mjs_monitor_summary",
 ]
 
 
@@ -244,6 +245,24 @@ class MjsSacTrainArgs(_Sized):
                 ("actor_lr", C.c_double), ("ent_coef", C.c_double), ("ent_coef_dev", C.c_void_p), ("entropy", C.POINTER(MjsEntropyStep))]
 
 
+class MjsMonitorState(_Sized):
+    """mjs_monitor_state: per-env episode accumulators, the optional quota, and the ring of finished episodes with its device cursor."""
+    _fields_ = [("struct_size", C.c_uint32), ("device", C.c_int32), ("num_envs", C.c_int32), ("window", C.c_int32), ("ep_return", C.c_void_p),
+                ("ep_length", C.c_void_p), ("ep_count", C.c_void_p), ("quota", C.c_void_p), ("cursor_dev", C.c_void_p), ("ring_return", C.c_void_p),
+                ("ring_length", C.c_void_p), ("ring_success", C.c_void_p), ("ring_terminated", C.c_void_p), ("ring_env", C.c_void_p)]
+
+
+class MjsMonitorBlock(_Sized):
+    """mjs_monitor_block: the [T, N] fields of a rollout block the episode statistics read, as DEVICE pointers."""
+    _fields_ = [("struct_size", C.c_uint32), ("T", C.c_int32), ("N", C.c_int32), ("autoreset", C.c_int32), ("reward", C.c_void_p),
+                ("terminated", C.c_void_p), ("truncated", C.c_void_p), ("is_success", C.c_void_p), ("step_type", C.c_void_p)]
+
+
+# the slots of mjs_monitor_summary's output (the MJS_MONITOR_* enum)
+MONITOR_SUMMARY_FIELDS = ("count", "return_mean", "return_std", "length_mean", "success_rate", "return_min", "return_max", "return_sum", "length_sum",
+                          "success_count")
+
+
 class MjsError(RuntimeError):
     pass
 
@@ -400,6 +419,10 @@ def lib() -> C.CDLL:
     L.mjs_actor_export.argtypes = [C.c_void_p, C.POINTER(MjsActorWeights), C.c_void_p]
     L.mjs_sac_draw_batch.argtypes = [C.POINTER(MjsReplayStorage), C.POINTER(MjsSacBatch), C.c_int32, C.c_uint64, C.c_uint64, C.c_void_p]
     L.mjs_sac_train.argtypes = [C.POINTER(MjsSacTrainArgs), C.c_void_p]
+    L.mjs_monitor_workspace_bytes.argtypes = [C.c_int32, C.c_int32]
+    L.mjs_monitor_workspace_bytes.restype = C.c_uint64
+    L.mjs_monitor_update.argtypes = [C.POINTER(MjsMonitorState), C.POINTER(MjsMonitorBlock), C.c_void_p, C.c_void_p]
+    L.mjs_monitor_summary.argtypes = [C.POINTER(MjsMonitorState), C.c_void_p, C.c_void_p]
     L.mjs_get_rng_state.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.mjs_set_rng_state.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = L

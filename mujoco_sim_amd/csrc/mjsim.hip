@@ -25,6 +25,7 @@
 #include "mjs_critic_train.h"
 #include "mjs_actor_train.h"
 #include "mjs_sac_train.h"
+#include "mjs_monitor.h"
 #ifdef MJS_STAMPS
 #include "mjs_stamps_report.h"
 #endif
@@ -2007,6 +2008,83 @@ int mjs_sac_train(const mjs_sac_train_args* a, void* stream) {
     if ((step + 1) % (uint64_t)a->target_update_interval == 0)
       if (int rc = mjs_critic_blend(a->target_critic, a->critic, a->tau, stream)) return rc;
   }
+  HIP_TRY(nullptr, hipGetLastError());
+  return MJS_OK;
+}
+
+// ---- episode statistics (mjs_monitor.h) -----------------------------------------------------------------------------------------
+// what mjs_monitor_update / mjs_monitor_summary refuse about a state descriptor; empty = fine
+static std::string monitor_state_refusal(const mjs_monitor_state* st) {
+  if (!st) return "state is null";
+  if (st->struct_size != sizeof(mjs_monitor_state)) return "mjs_monitor_state.struct_size does not match this library's header";
+  if (st->num_envs < 1) return "num_envs must be at least 1";
+  if (st->window < 1) return "window must be at least 1";
+  if (!st->ep_return || !st->ep_length || !st->ep_count) return "the state's ep_return, ep_length or ep_count is null";
+  if (!st->cursor_dev) return "cursor_dev is null";
+  if (!st->ring_return || !st->ring_length || !st->ring_success || !st->ring_terminated || !st->ring_env)
+    return "the ring's return, length, success, terminated or env is null";
+  return "";
+}
+
+uint64_t mjs_monitor_workspace_bytes(int32_t T, int32_t N) {
+  return T > 0 && N > 0 && (int64_t)T * N < ((int64_t)1 << 31) ? (uint64_t)mon::ws_bytes((int64_t)T * N) : 0;
+}
+
+int mjs_monitor_update(const mjs_monitor_state* st, const mjs_monitor_block* blk, void* workspace_dev, void* stream) {
+  const auto refuse = [](const std::string& why) { return fail(nullptr, MJS_ERR_INVALID_ARG, "mjs_monitor_update: " + why); };
+  if (std::string why = monitor_state_refusal(st); !why.empty()) return refuse(why);
+  if (!blk) return refuse("block is null");
+  if (blk->struct_size != sizeof(mjs_monitor_block)) return refuse("mjs_monitor_block.struct_size does not match this library's header");
+  if (blk->T < 0) return refuse("T is negative");
+  if (blk->N < 1) return refuse("N must be positive");
+  if (blk->N != st->num_envs) return refuse("the block's N is not the state's num_envs");
+  if (blk->autoreset != MJS_AUTORESET_NEXT_STEP && blk->autoreset != MJS_AUTORESET_SAME_STEP)
+    return refuse("the block's autoreset must be next-step or same-step (with auto-reset disabled a finished env starts no new episode)");
+  const bool same_step = blk->autoreset == MJS_AUTORESET_SAME_STEP;
+  const int64_t rows = (int64_t)blk->T * blk->N;
+  if (rows >= ((int64_t)1 << 31)) return refuse("T * N must stay below 2^31");
+  if (blk->T == 0) return MJS_OK;
+  if (!blk->reward || !blk->terminated || !blk->truncated || !blk->is_success) return refuse("reward, terminated, truncated or is_success is null");
+  if (!same_step && !blk->step_type) return refuse("next-step auto-reset needs step_type");
+  if (!workspace_dev) return refuse("workspace_dev is null");
+  if (int rc = device_refusal("mjs_monitor_update", st->device)) return rc;
+  DeviceGuard dev_(st->device);
+  HIP_TRY(nullptr, dev_.err);
+
+  mon::UpdateParams p{};
+  p.rows = rows; p.T = blk->T; p.N = blk->N; p.same_step = same_step; p.W = st->window;
+  p.ep_return = st->ep_return; p.ep_length = st->ep_length; p.ep_count = st->ep_count; p.quota = st->quota;
+  p.cursor = reinterpret_cast<unsigned long long*>(st->cursor_dev);
+  p.r_return = st->ring_return; p.r_length = st->ring_length; p.r_success = st->ring_success; p.r_terminated = st->ring_terminated; p.r_env = st->ring_env;
+  unsigned char* ws = static_cast<unsigned char*>(workspace_dev);
+  p.base = reinterpret_cast<unsigned long long*>(ws);
+  p.offsets = reinterpret_cast<uint32_t*>(ws + mon::WS_HEADER);
+  p.end_return = reinterpret_cast<double*>(ws + mon::WS_HEADER + mon::ws_offsets_bytes(rows));
+  p.end_length = reinterpret_cast<int32_t*>(ws + mon::WS_HEADER + mon::ws_offsets_bytes(rows) + (size_t)rows * sizeof(double));
+  p.reward = blk->reward; p.terminated = blk->terminated; p.truncated = blk->truncated; p.step_type = blk->step_type; p.is_success = blk->is_success;
+  const hipStream_t s = (hipStream_t)stream;
+  const dim3 chunks((unsigned)mon::n_chunks(rows));
+  mon::walk_kernel<<<dim3((unsigned)((blk->N + mon::THREADS - 1) / mon::THREADS)), mon::THREADS, 0, s>>>(p);
+  mon::count_kernel<<<chunks, mon::THREADS, 0, s>>>(p);
+  mon::scan_kernel<<<dim3(1), mon::THREADS, 0, s>>>(p);
+  mon::scatter_kernel<<<chunks, mon::THREADS, 0, s>>>(p);
+  HIP_TRY(nullptr, hipGetLastError());
+  return MJS_OK;
+}
+
+int mjs_monitor_summary(const mjs_monitor_state* st, double* out_dev, void* stream) {
+  const auto refuse = [](const std::string& why) { return fail(nullptr, MJS_ERR_INVALID_ARG, "mjs_monitor_summary: " + why); };
+  if (std::string why = monitor_state_refusal(st); !why.empty()) return refuse(why);
+  if (!out_dev) return refuse("out_dev is null");
+  if (int rc = device_refusal("mjs_monitor_summary", st->device)) return rc;
+  DeviceGuard dev_(st->device);
+  HIP_TRY(nullptr, dev_.err);
+  mon::SummaryParams p{};
+  p.W = st->window;
+  p.cursor = reinterpret_cast<const unsigned long long*>(st->cursor_dev);
+  p.r_return = st->ring_return; p.r_length = st->ring_length; p.r_success = st->ring_success;
+  p.out = out_dev;
+  mon::summary_kernel<<<dim3(1), mon::THREADS, 0, (hipStream_t)stream>>>(p);
   HIP_TRY(nullptr, hipGetLastError());
   return MJS_OK;
 }

@@ -15,6 +15,7 @@ import math
 import torch
 
 from . import _native as nat
+from .monitor import DeviceEpisodeMonitor, _run_evaluation
 from .policies import DeviceActor, DeviceActorOptimizer, DeviceCritic, DeviceCriticOptimizer, DeviceEntropyCoef, _is_linear
 from .replay import _ROLLOUT_KEEP, DeviceReplayBuffer
 
@@ -107,6 +108,9 @@ class DeviceSAC:
         self.venv, self.actor, self.critic, self.device = venv, actor, critic, actor.device
         self.num_timesteps = 0       # env steps taken by learn, summed over the envs
         self.num_gradient_steps = 0  # the gradient-step counter: the next step's batch is draw_batch(num_gradient_steps)
+        self.log = []                # learn's records (with log_interval or eval_freq)
+        self.eval_block_steps = 32   # evaluate_policy's block_steps and max_steps for learn's evaluations: with max_steps set, an eval_env whose
+        self.eval_max_steps = None   # episodes do not end raises MjsError after that many control steps per env instead of looping for ever
         self._size_checked = False
         self._scratch = None
         if actor._a is None:
@@ -324,28 +328,113 @@ class DeviceSAC:
         self.buffer.add_block(obs0, block)
         return block
 
-    def learn(self, total_timesteps, generator=None):
+    def _check_reporting(self, monitor, log_interval, eval_env, eval_freq, n_eval_episodes, callback):
+        """learn's reporting arguments checked (ValueError with the argument's name); True where records are to be made."""
+        if monitor is not None:
+            if not isinstance(monitor, DeviceEpisodeMonitor):
+                raise ValueError(f"monitor must be a DeviceEpisodeMonitor, got {type(monitor).__name__}")
+            if monitor.num_envs != int(self.venv.num_envs):
+                raise ValueError(f"monitor was made for {monitor.num_envs} envs, the env has {self.venv.num_envs}")
+            if monitor.device != torch.device(self.venv.device):
+                raise ValueError(f"monitor lives on {monitor.device}, the env on {self.venv.device}")
+        if log_interval is not None:
+            _int_in("log_interval", log_interval, 1, ">= 1 (training phases between records)")
+            if monitor is None:
+                raise ValueError("log_interval needs a monitor: the records hold its statistics")
+        if (eval_env is None) != (eval_freq is None):
+            raise ValueError("eval_env and eval_freq go together: give both or neither")
+        if eval_freq is not None:
+            _int_in("eval_freq", eval_freq, 1, ">= 1 (env steps summed over the envs between evaluations)")
+            _int_in("n_eval_episodes", n_eval_episodes, 1, ">= 1")
+            for attr in ("num_envs", "device", "reset", "actor_rollout"):
+                if not hasattr(eval_env, attr):
+                    raise ValueError(f"eval_env must be a HipVectorEnv, got {type(eval_env).__name__}")
+            if torch.device(eval_env.device) != self.device:
+                raise ValueError(f"eval_env lives on {eval_env.device}, the actor on {self.device}")
+            if getattr(eval_env, "autoreset", "next_step") not in ("next_step", "same_step"):
+                raise ValueError(f"eval_env runs autoreset={eval_env.autoreset!r}: a finished env starts no new episode")
+        reporting = log_interval is not None or eval_freq is not None
+        if callback is not None and not callable(callback):
+            raise ValueError(f"callback must be callable, got {type(callback).__name__}")
+        if callback is not None and not reporting:
+            raise ValueError("callback is called with every record: it needs log_interval or eval_freq")
+        return reporting
+
+    def _record(self, monitor):
+        """A log record with every documented key; the statistics not taken at this point are NaN."""
+        nan = float("nan")
+        record = {"num_timesteps": self.num_timesteps, "num_gradient_steps": self.num_gradient_steps, "rollout/ep_rew_mean": nan, "rollout/ep_len_mean": nan,
+                  "rollout/success_rate": nan, "eval/mean_reward": nan, "eval/std_reward": nan, "eval/success_rate": nan, "eval/mean_ep_length": nan}
+        if monitor is not None:
+            s = monitor.summary()
+            record.update({"rollout/ep_rew_mean": s["return_mean"], "rollout/ep_len_mean": s["length_mean"], "rollout/success_rate": s["success_rate"]})
+        return record
+
+    def _evaluate_into(self, record, eval_env, n_eval_episodes, monitor):
+        """SB3's EvalCallback step: ``n_eval_episodes`` deterministic episodes of the actor on ``eval_env``, into ``record``."""
+        ev = _run_evaluation(eval_env, self.actor, n_eval_episodes, True, self.eval_block_steps, self.eval_max_steps, None)
+        try:
+            s = ev.summary()
+        finally:
+            ev.close()
+        record.update({"eval/mean_reward": s["return_mean"], "eval/std_reward": s["return_std"], "eval/success_rate": s["success_rate"],
+                       "eval/mean_ep_length": s["length_mean"]})
+        if eval_env is self.venv:  # the training env ran the evaluation's episodes: collection continues from a reset state
+            self.venv.reset()
+            if monitor is not None:
+                monitor.reset_in_flight()
+
+    def learn(self, total_timesteps, generator=None, *, monitor=None, log_interval=None, eval_env=None, eval_freq=None, n_eval_episodes=5, callback=None):
         """Alternates ``buffer.collect(venv, actor, train_freq)`` with :meth:`train` until ``total_timesteps`` more env steps, summed over
         the envs, have been taken (whole blocks: ``train_freq * num_envs`` at a time). While ``num_timesteps < learning_starts`` the actions
         are uniform in the action space, drawn from ``generator``, which also gives the actor's draws afterwards; training starts once
         ``num_timesteps > learning_starts``, as in SB3. The env must have been reset. ``buffer.size`` is read ONCE, before the first
-        training phase (the one synchronisation here); an empty buffer raises. No callbacks, logging or evaluation. Returns ``self``."""
+        training phase (the one synchronisation here); an empty buffer raises. Returns ``self``.
+
+        Reporting (all off by default: the launches and the one read-back are then exactly the above). ``monitor``: a
+        :class:`DeviceEpisodeMonitor`, fed every collected block, warm-up blocks included (four launches per block, no synchronisation).
+        Every ``log_interval`` training phases, and every ``eval_freq`` env steps summed over the envs (SB3's count), a record is appended
+        to ``self.log`` and passed to ``callback(record)``: a dict with ``num_timesteps``, ``num_gradient_steps``, ``rollout/ep_rew_mean``,
+        ``rollout/ep_len_mean``, ``rollout/success_rate`` (the monitor's window; one small read-back per record) and ``eval/mean_reward``,
+        ``eval/std_reward``, ``eval/success_rate``, ``eval/mean_ep_length`` (:func:`evaluate_policy`'s loop on ``eval_env``: ``n_eval_episodes``
+        deterministic episodes, SB3's ``EvalCallback``); what a record did not take is NaN. ``eval_env`` may be ``self.venv``, as in the
+        reference's script: the env is then reset after the evaluation, the monitor's in-flight accumulators are zeroed and collection
+        continues from the reset state. The attributes ``eval_block_steps`` (32) and ``eval_max_steps`` (``None``: unbounded) are
+        :func:`evaluate_policy`'s ``block_steps`` and ``max_steps`` for these evaluations. Argument checks raise ``ValueError`` before anything native."""
         total = _int_in("total_timesteps", total_timesteps, 0, ">= 0")
+        reporting = self._check_reporting(monitor, log_interval, eval_env, eval_freq, n_eval_episodes, callback)
         self._open()
         N, T = int(self.venv.num_envs), self.train_freq
         end = self.num_timesteps + total
+        phases, next_eval = 0, self.num_timesteps + (eval_freq or 0)
         while self.num_timesteps < end:
             if self.num_timesteps < self.learning_starts:
-                self._collect_uniform(T, generator)
+                block = self._collect_uniform(T, generator)
             else:
-                self.buffer.collect(self.venv, self.actor, T, generator=generator)
+                block = self.buffer.collect(self.venv, self.actor, T, generator=generator)
+            if monitor is not None:
+                monitor.update(block, self.buffer.autoreset)
             self.num_timesteps += T * N
-            if self.num_timesteps > self.learning_starts:
+            trained = self.num_timesteps > self.learning_starts
+            if trained:
                 if not self._size_checked:
                     if self.buffer.size == 0:
                         raise nat.MjsError("the replay buffer is empty after the collected blocks: nothing to train on")
                     self._size_checked = True
                 self.train(self._gradient_steps_per_phase())
+            if reporting:
+                phases += trained
+                record = None
+                if log_interval is not None and trained and phases % log_interval == 0:
+                    record = self._record(monitor)
+                if eval_freq is not None and self.num_timesteps >= next_eval:
+                    record = record or self._record(monitor)
+                    self._evaluate_into(record, eval_env, n_eval_episodes, monitor)
+                    next_eval += -(-(self.num_timesteps - next_eval + 1) // eval_freq) * eval_freq  # the first multiple past num_timesteps
+                if record is not None:
+                    self.log.append(record)
+                    if callback is not None:
+                        callback(record)
         return self
 
     # ------------------------------------------------------------------ SB3
