@@ -631,6 +631,70 @@ int mjs_critic_blend(mjs_critic* dst_critic, const mjs_critic* src_critic, doubl
  * n_critics). One small launch per layer. MJS_ERR_INVALID_ARG for a null pointer, a wrong struct_size or a critic never loaded. */
 int mjs_critic_export(const mjs_critic* critic, const mjs_critic_weights* weights_out, void* stream);
 
+/* The encoder's backward pass, Adam step, blend and export on the device (csrc/mjs_encoder_train.h; entry points added after abi 3 as
+ * well). From frames rgb [n, H, W, 3] and an upstream gradient dfeatures [n, F] (float32, read as it is: the 1/B of a mean loss is the
+ * caller's business, as with autograd), the gradient of sum(features * dfeatures) with respect to the eight parameter tensors of the
+ * NatureCNN that mjs_encoder_features evaluates - torch's features.backward(dfeatures). float32 with float32 accumulation; ReLU's
+ * derivative is 1 where the stored activation is > 0 and 0 otherwise; no gradient with respect to the image. The encoder's PACKED copy
+ * becomes the master copy of the parameters: mjs_encoder_features and the visual rollout see every step at once, a target encoder blends
+ * from it (mjs_encoder_blend), mjs_encoder_export writes torch tensors, and mjs_encoder_load would overwrite the trained parameters.
+ *
+ * The sums over the batch are bitwise reproducible (no atomics): split s owns the contiguous images [s * images_per_split,
+ * (s + 1) * images_per_split) and stores one partial slab; the slabs are summed in order. With
+ *   slab = 192*32 + 32 + 512*64 + 64 + 576*64 + 64 + n_flatten*Fp + Fp + 4 floats  (Fp = F rounded up to 32),
+ *   splits_max = min(64, max(1, 128 MiB / (4 * slab))),  images_per_split = ceil(n / splits_max),  splits = ceil(n / images_per_split),
+ * a function of n and the shape alone.
+ *
+ * The workspace, float32, in this order (P1, P2, P3 = output positions H1*W1, H2*W2, H3*W3 of the three convolutions; every block
+ * starts on a multiple of 4 floats):
+ *   conv1 [n, P1, 32] | conv2 [n, P2, 64] | flat [n, n_flatten]            the post-ReLU activations (flat in CHW order)
+ *   features [n, F] (n*F rounded up to 4) | Gf [n, Fp]                     Gf = dfeatures where features > 0, else 0
+ *   dZ3 [n, P3, 64] | dZ2 [n, P2, 64] | dZ1 [n, P1, 32]                    gradients at the convolutions' pre-activations
+ *   slabs [splits][slab]
+ * so mjs_encoder_train_workspace_bytes = 4 * (2*n*P1*32 + 2*n*P2*64 + 2*n*n_flatten + roundup4(n*F) + n*Fp + splits*slab). */
+typedef struct mjs_encoder_opt mjs_encoder_opt;
+typedef struct {
+  uint32_t struct_size;      /* sizeof(mjs_encoder_opt_desc) */
+  int32_t reserved0;         /* 0 */
+  double lr;                 /* >= 0; kept for reference, mjs_encoder_update takes lr per call */
+  double beta1;              /* [0, 1) */
+  double beta2;              /* [0, 1) */
+  double eps;                /* > 0 */
+} mjs_encoder_opt_desc;      /* 40 bytes */
+/* An optimiser is bound to ONE loaded encoder, which must outlive it. It owns zeroed first and second moments and the step count t = 0.
+ * MJS_ERR_INVALID_ARG for a null pointer, a wrong struct_size, an encoder that was never loaded, lr < 0, a beta outside [0, 1) or eps <= 0. */
+int mjs_encoder_opt_create(mjs_encoder* enc, const mjs_encoder_opt_desc* desc, mjs_encoder_opt** out);
+void mjs_encoder_opt_destroy(mjs_encoder_opt* opt);
+/* Bytes of the workspace above for n images; 0 for a null encoder or n <= 0. */
+uint64_t mjs_encoder_train_workspace_bytes(const mjs_encoder* enc, int32_t n);
+typedef struct {
+  uint32_t struct_size;                  /* sizeof(mjs_encoder_grad_args) */
+  int32_t n;                             /* images: >= 0 */
+  const uint8_t* rgb_dev;                /* [n, height, width, 3], required */
+  const float* dfeatures_dev;            /* [n, F], required */
+  void* workspace_dev;                   /* mjs_encoder_train_workspace_bytes(enc, n) bytes, 16-byte aligned, overwritten; required */
+  float* features_out_dev;               /* [n, F] or NULL: mjs_encoder_features' values bit for bit */
+  const mjs_encoder_weights* grads_out;  /* HOST struct of DEVICE pointers the gradients are WRITTEN to, torch layout, or NULL
+                                          * (mjs_encoder_grad only; all eight must be given) */
+  float* activations_out_dev[3];         /* each NULL or WRITTEN: conv1 [n, P1, 32], conv2 [n, P2, 64], flat [n, n_flatten], post-ReLU */
+} mjs_encoder_grad_args;                 /* 72 bytes */
+/* The forward (which keeps the activations) and the backward, and no update: t and the parameters stay. Eight launches, five small ones
+ * more where grads_out is given, one device-to-device copy per optional output. MJS_ERR_INVALID_ARG (nothing launched, text in
+ * mjs_last_error(NULL)) for a null argument or required pointer, a wrong struct_size, n < 0, an encoder that was never loaded or an
+ * optimiser of another encoder. n == 0 does nothing and returns 0. Nothing is read back, nothing synchronises. */
+int mjs_encoder_grad(const mjs_encoder* enc, mjs_encoder_opt* opt, const mjs_encoder_grad_args* args, void* stream);
+/* One gradient step of the optimiser's encoder: mjs_encoder_grad's launches, then Adam over the packed copy by the lines and the
+ * coefficient rule of mjs_critic_update (one launch), t += 1. The padding of the packed copy has zero gradient and stays zero. Refusals
+ * as mjs_encoder_grad's, and lr < 0 or a non-NULL grads_out. n == 0 does nothing (t stays). */
+int mjs_encoder_update(mjs_encoder_opt* opt, const mjs_encoder_grad_args* args, double lr, void* stream);
+/* dst = (1 - tau) * dst + tau * src between the packed copies of two encoders (polyak_update for a target critic's own extractor), one
+ * launch, mjs_critic_blend's formula and rounding; tau == 1 copies and does not read dst. MJS_ERR_INVALID_ARG for a null encoder,
+ * encoders of different shapes or devices, a src that was never loaded, tau outside (0, 1], or tau != 1 into a dst never loaded. */
+int mjs_encoder_blend(mjs_encoder* dst_enc, const mjs_encoder* src_enc, double tau, void* stream);
+/* The packed copy back into torch layout (Conv2d [out, in, kh, kw], Linear [F, n_flatten]): weights_out holds DEVICE pointers that are
+ * WRITTEN. Four small launches. MJS_ERR_INVALID_ARG for a null pointer, a wrong struct_size or an encoder never loaded. */
+int mjs_encoder_export(const mjs_encoder* enc, const mjs_encoder_weights* weights_out, void* stream);
+
 /* The actor and entropy-coefficient update of SAC.train on the device (csrc/mjs_actor_train.h; entry points added after abi 3 as well):
  *   a, logp = actor.action_log_prob(obs)  on the caller's draws z, as mjs_sac_td_target computes a' and logp
  *   actor_loss = mean(ent_coef * logp - min_c Q_c(obs, a));  zero_grad, backward, torch.optim.Adam.step on the ACTOR alone

@@ -18,8 +18,8 @@ from .environments.tasks.point_reach import PointMassReachTask
 from .environments.tasks.robot_reach import RobotReachConfig, RobotReachTask
 from .environments.tasks.robot_push_button import RobotPushButtonTask
 from .environments.tasks.robot_planar_push import RobotPushConfig, RobotPushTask
-from .policies import (DeviceActor, DeviceActorOptimizer, DeviceCritic, DeviceCriticOptimizer, DeviceEncoder, DeviceEntropyCoef,  # noqa: F401
-                       sac_gradient_step, sac_td_target)
+from .policies import (DeviceActor, DeviceActorOptimizer, DeviceCritic, DeviceCriticOptimizer, DeviceEncoder, DeviceEncoderOptimizer,  # noqa: F401
+                       DeviceEntropyCoef, sac_gradient_step, sac_td_target)
 from .monitor import DeviceEpisodeMonitor, evaluate_policy  # noqa: F401
 from .recording import LeRobotDatasetRecorder  # noqa: F401
 from .replay import DeviceReplayBuffer  # noqa: F401

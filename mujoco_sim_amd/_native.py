@@ -56,6 +56,8 @@ EXPORTED_SYMBOLS = [
     "mjs_critic_export",
     "mjs_actor_opt_create", "mjs_actor_opt_destroy", "mjs_actor_train_workspace_bytes", "mjs_actor_grad", "mjs_actor_update", "mjs_actor_export",
     "mjs_sac_draw_batch", "mjs_sac_train",
+    "mjs_encoder_opt_create", "mjs_encoder_opt_destroy", "mjs_encoder_train_workspace_bytes", "mjs_encoder_grad", "mjs_encoder_update", "mjs_encoder_blend",
+    "mjs_encoder_export",
     "mjs_monitor_workspace_bytes", "mjs_monitor_update", "mjs_monitor_summary",
 ]
 
@@ -212,6 +214,17 @@ class MjsCriticGradArgs(_Sized):
 class MjsActorOptDesc(_Sized):
     """mjs_actor_opt_desc: Adam's settings for an actor's packed copy."""
     _fields_ = [("struct_size", C.c_uint32), ("reserved0", C.c_int32), ("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double)]
+
+
+class MjsEncoderOptDesc(_Sized):
+    """mjs_encoder_opt_desc: Adam's settings for an encoder's packed copy."""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved0", C.c_int32), ("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double)]
+
+
+class MjsEncoderGradArgs(_Sized):
+    """mjs_encoder_grad_args: the frames, the upstream gradient, the workspace, and where mjs_encoder_grad / mjs_encoder_update write."""
+    _fields_ = [("struct_size", C.c_uint32), ("n", C.c_int32), ("rgb_dev", C.c_void_p), ("dfeatures_dev", C.c_void_p), ("workspace_dev", C.c_void_p),
+                ("features_out_dev", C.c_void_p), ("grads_out", C.POINTER(MjsEncoderWeights)), ("activations_out_dev", C.c_void_p * 3)]
 
 
 class MjsEntropyStep(_Sized):
@@ -417,6 +430,15 @@ def lib() -> C.CDLL:
     L.mjs_actor_grad.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(MjsActorGradArgs), C.c_void_p]
     L.mjs_actor_update.argtypes = [C.c_void_p, C.POINTER(MjsActorGradArgs), C.c_double, C.c_void_p]
     L.mjs_actor_export.argtypes = [C.c_void_p, C.POINTER(MjsActorWeights), C.c_void_p]
+    L.mjs_encoder_opt_create.argtypes = [C.c_void_p, C.POINTER(MjsEncoderOptDesc), C.POINTER(C.c_void_p)]
+    L.mjs_encoder_opt_destroy.argtypes = [C.c_void_p]
+    L.mjs_encoder_opt_destroy.restype = None
+    L.mjs_encoder_train_workspace_bytes.argtypes = [C.c_void_p, C.c_int32]
+    L.mjs_encoder_train_workspace_bytes.restype = C.c_uint64
+    L.mjs_encoder_grad.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(MjsEncoderGradArgs), C.c_void_p]
+    L.mjs_encoder_update.argtypes = [C.c_void_p, C.POINTER(MjsEncoderGradArgs), C.c_double, C.c_void_p]
+    L.mjs_encoder_blend.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_void_p]
+    L.mjs_encoder_export.argtypes = [C.c_void_p, C.POINTER(MjsEncoderWeights), C.c_void_p]
     L.mjs_sac_draw_batch.argtypes = [C.POINTER(MjsReplayStorage), C.POINTER(MjsSacBatch), C.c_int32, C.c_uint64, C.c_uint64, C.c_void_p]
     L.mjs_sac_train.argtypes = [C.POINTER(MjsSacTrainArgs), C.c_void_p]
     L.mjs_monitor_workspace_bytes.argtypes = [C.c_int32, C.c_int32]

@@ -140,8 +140,20 @@ __device__ __forceinline__ void conv(const uint8_t* img, const float* lut, int R
   }
 }
 
-// grid = N workgroups of WAVES wavefronts; dynamic LDS = lds_bytes(geometry)
-__global__ __launch_bounds__(WAVES * 64) void conv_kernel(ConvParams p) {
+// The LDS activations of one env [P][S floats] -> dst [P][C], 16 bytes per thread and step (KEEP below)
+template <int C, int S>
+__device__ __forceinline__ void store_activations(const float* Y, int P, float* __restrict__ dst, int tid) {
+  for (int e = tid; e < P * (C / 4); e += WAVES * 64) {
+    const int pos = e / (C / 4), j = e - pos * (C / 4);
+    *reinterpret_cast<f32x4*>(dst + (size_t)e * 4) = *reinterpret_cast<const f32x4*>(Y + pos * S + 4 * j);
+  }
+}
+
+// The three convolutions of one workgroup's env: conv_kernel's body, shared with the training forward (mjs_encoder_train.h), which
+// KEEPs the post-ReLU outputs of conv1 in keep1 [N, P1, 32] and of conv2 in keep2 [N, P2, 64] (copies of the LDS images; `flat` is
+// conv3's). The arithmetic does not depend on KEEP.
+template <bool KEEP>
+__device__ __forceinline__ void convs(const ConvParams& p, float* keep1, float* keep2) {
   extern __shared__ __attribute__((aligned(16))) unsigned char enc_lds[];
   const Geometry& g = p.g;
   float* lut = reinterpret_cast<float*>(enc_lds);
@@ -162,10 +174,15 @@ __global__ __launch_bounds__(WAVES * 64) void conv_kernel(ConvParams p) {
   __syncthreads();
   conv<8, 8, 4, C_IN, C1, true, false>(img, lut, g.RS, nullptr, 0, g.W, g.W1, g.H1 * g.W1, c1, S1, p.W1, p.B1, wave, lane);
   __syncthreads();
+  if (KEEP) store_activations<C1, S1>(c1, g.H1 * g.W1, keep1 + (size_t)env * g.H1 * g.W1 * C1, tid);
   conv<4, 4, 2, C1, C2, false, false>(nullptr, nullptr, 0, c1, S1, g.W1, g.W2, g.H2 * g.W2, c2, S2, p.W2, p.B2, wave, lane);
   __syncthreads();
+  if (KEEP) store_activations<C2, S2>(c2, g.H2 * g.W2, keep2 + (size_t)env * g.H2 * g.W2 * C2, tid);
   conv<3, 3, 1, C2, C3, false, true>(nullptr, nullptr, 0, c2, S2, g.W2, g.W3, g.H3 * g.W3, p.flat + (size_t)env * g.n_flatten, 0, p.W3, p.B3, wave, lane);
 }
+
+// grid = N workgroups of WAVES wavefronts; dynamic LDS = lds_bytes(geometry)
+__global__ __launch_bounds__(WAVES * 64) void conv_kernel(ConvParams p) { convs<false>(p, nullptr, nullptr); }
 static_assert(WAVES * 64 == 256, "the table of quotients has one entry per thread");
 
 struct FcParams {

@@ -24,6 +24,7 @@
 #include "mjs_critic.h"
 #include "mjs_critic_train.h"
 #include "mjs_actor_train.h"
+#include "mjs_encoder_train.h"
 #include "mjs_sac_train.h"
 #include "mjs_monitor.h"
 #ifdef MJS_STAMPS
@@ -189,6 +190,17 @@ struct mjs_encoder {
   float* w[4] = {nullptr, nullptr, nullptr, nullptr};  // packed [k][out]: conv1..3, fc
   float* b[4] = {nullptr, nullptr, nullptr, nullptr};
   bool loaded = false;
+};
+
+// Adam on an encoder's packed copy (mjs_encoder_train.h): the moments and the step count. The slabs live in the caller's workspace.
+struct mjs_encoder_opt {
+  mjs_encoder* encoder = nullptr;  // the encoder it was created for; must outlive the optimiser
+  mjs_encoder_opt_desc desc;
+  crit::Layout L;
+  float* m = nullptr;              // [L.total], slab layout
+  float* v = nullptr;
+  float* gsum = nullptr;           // [L.total]: the summed gradient on its way to torch layout
+  int64_t t = 0;                   // optimiser steps taken
 };
 
 namespace {
@@ -1908,6 +1920,251 @@ int mjs_actor_export(const mjs_actor* a, const mjs_actor_weights* out, void* str
   HIP_TRY(nullptr, dev_.err);
   const crit::Packed P = actor_packed_of(a);
   launch_actor_unpack(a, P.seg, out, (hipStream_t)stream);
+  HIP_TRY(nullptr, hipGetLastError());
+  return MJS_OK;
+}
+
+// ---- the encoder's backward pass, Adam step, blend and export (mjs_encoder_train.h) ----------------------------------------------
+// where an encoder's layers sit in a slab: conv1..3 and fc, weights then bias each
+static crit::Layout encoder_layout_of(const mjs_encoder* e) {
+  const int K[4] = {8 * 8 * enc::C_IN, 4 * 4 * enc::C1, 3 * 3 * enc::C2, e->g.n_flatten};
+  const int O[4] = {enc::C1, enc::C2, enc::C3, e->Fp};
+  crit::Layout L{};
+  int at = 0;
+  for (int l = 0; l < 4; l++) {
+    L.off[2 * l] = at;
+    at += K[l] * O[l];
+    L.off[2 * l + 1] = at;
+    at += O[l];
+  }
+  L.off[8] = at;
+  L.total = at + 4;
+  return L;
+}
+static crit::Packed encoder_packed_of(const mjs_encoder* e) {
+  crit::Packed P;
+  for (int l = 0; l < 4; l++) { P.seg[2 * l] = e->w[l]; P.seg[2 * l + 1] = e->b[l]; }
+  return P;
+}
+static bool encoder_tensors_given(const mjs_encoder_weights* w) {
+  return w->conv1_w && w->conv1_b && w->conv2_w && w->conv2_b && w->conv3_w && w->conv3_b && w->fc_w && w->fc_b;
+}
+// packed layers (the segments of the encoder's copy or of a summed slab) -> torch layout: one small launch per layer
+static void launch_encoder_unpack(const mjs_encoder* e, const float* const* seg, const mjs_encoder_weights* out, hipStream_t s) {
+  const enct::UnpackConvParams conv[3] = {{seg[0], seg[1], enc::C1, enc::C_IN, 8, 8, const_cast<float*>(out->conv1_w), const_cast<float*>(out->conv1_b)},
+                                          {seg[2], seg[3], enc::C2, enc::C1, 4, 4, const_cast<float*>(out->conv2_w), const_cast<float*>(out->conv2_b)},
+                                          {seg[4], seg[5], enc::C3, enc::C2, 3, 3, const_cast<float*>(out->conv3_w), const_cast<float*>(out->conv3_b)}};
+  for (const enct::UnpackConvParams& p : conv)
+    enct::unpack_conv_kernel<<<dim3((unsigned)((p.kh * p.kw * p.cin * p.cout + 255) / 256)), 256, 0, s>>>(p);
+  crit::UnpackParams p;
+  p.src_w = seg[6]; p.src_b = seg[7];
+  p.K = e->g.n_flatten; p.O = e->Fp;
+  p.in = e->g.n_flatten; p.out = e->desc.features_dim;
+  p.dst_w = const_cast<float*>(out->fc_w); p.dst_b = const_cast<float*>(out->fc_b);
+  crit::unpack_kernel<<<dim3((unsigned)((p.out * p.in + 255) / 256)), 256, 0, s>>>(p);
+}
+
+int mjs_encoder_opt_create(mjs_encoder* e, const mjs_encoder_opt_desc* desc, mjs_encoder_opt** out) {
+  const std::string name = "mjs_encoder_opt_create";
+  const auto refuse = [&](const std::string& why) { return fail(nullptr, MJS_ERR_INVALID_ARG, name + ": " + why); };
+  if (out) *out = nullptr;
+  if (!e || !desc || !out) return refuse("null argument");
+  if (desc->struct_size != sizeof(mjs_encoder_opt_desc)) return refuse("mjs_encoder_opt_desc.struct_size does not match this library's header");
+  if (!e->loaded) return refuse("the encoder has no parameters yet (mjs_encoder_load)");
+  if (!(desc->lr >= 0.0) || !std::isfinite(desc->lr)) return refuse("lr must be finite and >= 0");
+  if (!(desc->beta1 >= 0.0 && desc->beta1 < 1.0) || !(desc->beta2 >= 0.0 && desc->beta2 < 1.0)) return refuse("beta1 and beta2 must lie in [0, 1)");
+  if (!(desc->eps > 0.0) || !std::isfinite(desc->eps)) return refuse("eps must be finite and > 0");
+  DeviceGuard dev_(e->desc.device);
+  std::unique_ptr<mjs_encoder_opt, void (*)(mjs_encoder_opt*)> guard(new (std::nothrow) mjs_encoder_opt(), mjs_encoder_opt_destroy);
+  mjs_encoder_opt* o = guard.get();
+  if (!o) return fail(nullptr, MJS_ERR_ALLOC, name + ": out of host memory");
+  CREATE_TRY(name, dev_.err);
+  o->encoder = e;
+  o->desc = *desc;
+  o->L = encoder_layout_of(e);
+  const size_t per = sizeof(float) * (size_t)o->L.total;
+  CREATE_TRY(name, hipMalloc(&o->m, per));
+  CREATE_TRY(name, hipMalloc(&o->v, per));
+  CREATE_TRY(name, hipMalloc(&o->gsum, per));
+  CREATE_TRY(name, hipMemset(o->m, 0, per));
+  CREATE_TRY(name, hipMemset(o->v, 0, per));
+  CREATE_TRY(name, hipDeviceSynchronize());  // the moments are zero before any stream's first step
+  CREATE_TRY(name, hipFuncSetAttribute(reinterpret_cast<const void*>(&enct::forward_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       (int)enc::lds_bytes(enc::geometry(enc::MAX_HW, enc::MAX_HW))));
+  *out = guard.release();
+  return MJS_OK;
+}
+
+void mjs_encoder_opt_destroy(mjs_encoder_opt* o) {
+  if (!o) return;
+  free_all({o->m, o->v, o->gsum});
+  delete o;
+}
+
+uint64_t mjs_encoder_train_workspace_bytes(const mjs_encoder* e, int32_t n) {
+  if (!e || n <= 0) return 0;
+  const crit::Layout L = encoder_layout_of(e);
+  return (uint64_t)enct::workspace(e->g, e->desc.features_dim, e->Fp, n, enct::split_rule(n, L.total).splits, L.total).total * sizeof(float);
+}
+
+// what mjs_encoder_grad and mjs_encoder_update refuse alike; "" = fine
+static std::string encoder_grad_refusal(const mjs_encoder* e, const mjs_encoder_opt* o, const mjs_encoder_grad_args* args) {
+  if (!e || !o || !args) return "encoder, optimiser or args is null";
+  if (args->struct_size != sizeof(mjs_encoder_grad_args)) return "mjs_encoder_grad_args.struct_size does not match this library's header";
+  if (o->encoder != e) return "the optimiser was created for another encoder";
+  if (!e->loaded) return "the encoder has no parameters yet (mjs_encoder_load)";
+  if (args->n < 0) return "n is negative";
+  if (args->n > 0 && (!args->rgb_dev || !args->dfeatures_dev || !args->workspace_dev)) return "rgb_dev, dfeatures_dev or workspace_dev is null";
+  return "";
+}
+// the forward and the backward into the workspace's slabs; returns the splits written
+static int launch_encoder_grad(const mjs_encoder* e, const mjs_encoder_opt* o, const mjs_encoder_grad_args* args, hipStream_t s) {
+  const enc::Geometry& g = e->g;
+  const int n = args->n, F = e->desc.features_dim, Fp = e->Fp, NF = g.n_flatten;
+  const int P1 = g.H1 * g.W1, P2 = g.H2 * g.W2, P3 = g.H3 * g.W3;
+  const enct::Split sp = enct::split_rule(n, o->L.total);
+  const enct::Workspace w = enct::workspace(g, F, Fp, n, sp.splits, o->L.total);
+  float* ws = static_cast<float*>(args->workspace_dev);
+  enct::ForwardParams fw;
+  fw.c.N = n; fw.c.g = g; fw.c.rgb = args->rgb_dev;
+  fw.c.W1 = e->w[0]; fw.c.B1 = e->b[0]; fw.c.W2 = e->w[1]; fw.c.B2 = e->b[1]; fw.c.W3 = e->w[2]; fw.c.B3 = e->b[2];
+  fw.c.flat = ws + w.flat; fw.a1 = ws + w.a1; fw.a2 = ws + w.a2;
+  enct::forward_kernel<<<dim3((unsigned)n), enc::WAVES * 64, enc::lds_bytes(g), s>>>(fw);
+  enc::FcParams f;
+  f.N = n; f.K = NF; f.F = F; f.Fp = Fp;
+  f.flat = ws + w.flat; f.W = e->w[3]; f.B = e->b[3]; f.out = ws + w.feat;
+  enc::fc_kernel<<<dim3((unsigned)((n + enc::FC_TE - 1) / enc::FC_TE)), enc::WAVES * 64, 0, s>>>(f);
+  enct::FcBwdParams fb;
+  fb.N = n; fb.K = NF; fb.F = F; fb.Fp = Fp; fb.P3 = P3;
+  fb.dfeatures = args->dfeatures_dev; fb.features = ws + w.feat; fb.flat = ws + w.flat; fb.W = e->w[3];
+  fb.gf = ws + w.gf; fb.dz3 = ws + w.dz3;
+  enct::fc_bwd_kernel<<<dim3((unsigned)((n + enc::FC_TE - 1) / enc::FC_TE), (unsigned)((NF + enct::FCB_KBLOCK - 1) / enct::FCB_KBLOCK)), enc::WAVES * 64, 0, s>>>(fb);
+  enct::DgradParams dg;
+  dg.N = n; dg.g = g; dg.W2 = e->w[1]; dg.W3 = e->w[2]; dg.a1 = ws + w.a1; dg.a2 = ws + w.a2;
+  dg.dz3 = ws + w.dz3; dg.dz2 = ws + w.dz2; dg.dz1 = ws + w.dz1;
+  enct::dgrad_kernel<<<dim3((unsigned)n), enc::WAVES * 64, enct::dgrad_lds_bytes(g), s>>>(dg);
+  float* slab = ws + w.slabs;
+  enct::WgradParams wp{};
+  wp.n = n; wp.images_per_split = sp.images_per_split; wp.slab_stride = (size_t)o->L.total;
+  const auto grid = [&](int K, int O) { return dim3((unsigned)sp.splits, (unsigned)((K + enct::KBLOCK - 1) / enct::KBLOCK), (unsigned)(O / enct::OBLOCK)); };
+  wp.P = 1; wp.Wout = 1; wp.Pin = 1; wp.Win = 1; wp.K = NF; wp.O = Fp;
+  wp.rgb = nullptr; wp.X = ws + w.flat; wp.G = ws + w.gf; wp.dW = slab + o->L.off[6]; wp.dB = slab + o->L.off[7];
+  enct::wgrad_kernel<enct::SRC_FLAT, 1, 1, 1, 1><<<grid(wp.K, wp.O), enc::WAVES * 64, 0, s>>>(wp);
+  wp.P = P3; wp.Wout = g.W3; wp.Pin = P2; wp.Win = g.W2; wp.K = 3 * 3 * enc::C2; wp.O = enc::C3;
+  wp.X = ws + w.a2; wp.G = ws + w.dz3; wp.dW = slab + o->L.off[4]; wp.dB = slab + o->L.off[5];
+  enct::wgrad_kernel<enct::SRC_ACT, 3, 3, 1, enc::C2><<<grid(wp.K, wp.O), enc::WAVES * 64, 0, s>>>(wp);
+  wp.P = P2; wp.Wout = g.W2; wp.Pin = P1; wp.Win = g.W1; wp.K = 4 * 4 * enc::C1; wp.O = enc::C2;
+  wp.X = ws + w.a1; wp.G = ws + w.dz2; wp.dW = slab + o->L.off[2]; wp.dB = slab + o->L.off[3];
+  enct::wgrad_kernel<enct::SRC_ACT, 4, 4, 2, enc::C1><<<grid(wp.K, wp.O), enc::WAVES * 64, 0, s>>>(wp);
+  wp.P = P1; wp.Wout = g.W1; wp.Pin = g.H * g.W; wp.Win = g.W; wp.K = 8 * 8 * enc::C_IN; wp.O = enc::C1;
+  wp.rgb = args->rgb_dev; wp.X = nullptr; wp.G = ws + w.dz1; wp.dW = slab + o->L.off[0]; wp.dB = slab + o->L.off[1];
+  enct::wgrad_kernel<enct::SRC_IMAGE, 8, 8, 4, enc::C_IN><<<grid(wp.K, wp.O), enc::WAVES * 64, 0, s>>>(wp);
+  // the optional copies out of the workspace (device to device, on the stream)
+  const struct { float* dst; size_t at, count; } copies[4] = {{args->features_out_dev, w.feat, (size_t)n * F},
+                                                              {args->activations_out_dev[0], w.a1, (size_t)n * P1 * enc::C1},
+                                                              {args->activations_out_dev[1], w.a2, (size_t)n * P2 * enc::C2},
+                                                              {args->activations_out_dev[2], w.flat, (size_t)n * NF}};
+  for (const auto& c : copies)
+    if (c.dst) (void)hipMemcpyAsync(c.dst, ws + c.at, c.count * sizeof(float), hipMemcpyDeviceToDevice, s);
+  return sp.splits;
+}
+static crit::SumParams encoder_sum_params(const mjs_encoder_opt* o, const mjs_encoder_grad_args* args, int splits, const enct::Workspace& w) {
+  crit::SumParams p{};
+  p.L = o->L; p.n_critics = 1; p.splits = splits;
+  p.inv_B = 1.0f;
+  p.slabs = static_cast<const float*>(args->workspace_dev) + w.slabs; p.loss = nullptr;
+  return p;
+}
+static enct::Workspace encoder_workspace_of(const mjs_encoder* e, const mjs_encoder_opt* o, int n) {
+  return enct::workspace(e->g, e->desc.features_dim, e->Fp, n, enct::split_rule(n, o->L.total).splits, o->L.total);
+}
+
+int mjs_encoder_grad(const mjs_encoder* e, mjs_encoder_opt* o, const mjs_encoder_grad_args* args, void* stream) {
+  const auto refuse = [](const std::string& why) { return fail(nullptr, MJS_ERR_INVALID_ARG, "mjs_encoder_grad: " + why); };
+  const std::string why = encoder_grad_refusal(e, o, args);
+  if (!why.empty()) return refuse(why);
+  if (args->grads_out) {
+    if (args->grads_out->struct_size != sizeof(mjs_encoder_weights)) return refuse("mjs_encoder_weights.struct_size does not match this library's header");
+    if (!encoder_tensors_given(args->grads_out)) return refuse("grads_out: a weight or bias pointer is null");
+  }
+  if (args->n == 0) return MJS_OK;
+  DeviceGuard dev_(e->desc.device);
+  HIP_TRY(nullptr, dev_.err);
+  const hipStream_t s = (hipStream_t)stream;
+  const int splits = launch_encoder_grad(e, o, args, s);
+  if (args->grads_out) {
+    crit::slab_sum_kernel<<<dim3((unsigned)((o->L.off[8] + 1 + 255) / 256), 1), 256, 0, s>>>(encoder_sum_params(o, args, splits, encoder_workspace_of(e, o, args->n)), o->gsum);
+    const float* seg[8];
+    for (int k = 0; k < 8; k++) seg[k] = o->gsum + o->L.off[k];
+    launch_encoder_unpack(e, seg, args->grads_out, s);
+  }
+  HIP_TRY(nullptr, hipGetLastError());
+  return MJS_OK;
+}
+
+int mjs_encoder_update(mjs_encoder_opt* o, const mjs_encoder_grad_args* args, double lr, void* stream) {
+  const auto refuse = [](const std::string& why) { return fail(nullptr, MJS_ERR_INVALID_ARG, "mjs_encoder_update: " + why); };
+  const std::string why = encoder_grad_refusal(o ? o->encoder : nullptr, o, args);
+  if (!why.empty()) return refuse(why);
+  if (!(lr >= 0.0) || !std::isfinite(lr)) return refuse("lr must be finite and >= 0");
+  if (args->grads_out) return refuse("grads_out must be null (mjs_encoder_grad returns gradients)");
+  if (args->n == 0) return MJS_OK;
+  mjs_encoder* e = o->encoder;
+  DeviceGuard dev_(e->desc.device);
+  HIP_TRY(nullptr, dev_.err);
+  const hipStream_t s = (hipStream_t)stream;
+  const int splits = launch_encoder_grad(e, o, args, s);
+  const double t = (double)(o->t + 1);
+  crit::AdamParams p{};
+  p.s = encoder_sum_params(o, args, splits, encoder_workspace_of(e, o, args->n));
+  p.net[0] = encoder_packed_of(e);
+  p.m = o->m; p.v = o->v;
+  p.one_minus_beta1 = (float)(1.0 - o->desc.beta1);
+  p.beta2 = (float)o->desc.beta2;
+  p.one_minus_beta2 = (float)(1.0 - o->desc.beta2);
+  p.sqrt_bc2 = (float)std::sqrt(1.0 - std::pow(o->desc.beta2, t));
+  p.eps = (float)o->desc.eps;
+  p.step_size = (float)(lr / (1.0 - std::pow(o->desc.beta1, t)));
+  crit::adam_kernel<<<dim3((unsigned)((o->L.off[8] + 1 + 255) / 256), 1), 256, 0, s>>>(p);
+  HIP_TRY(nullptr, hipGetLastError());
+  o->t += 1;
+  return MJS_OK;
+}
+
+int mjs_encoder_blend(mjs_encoder* dst, const mjs_encoder* src, double tau, void* stream) {
+  const auto refuse = [](const std::string& why) { return fail(nullptr, MJS_ERR_INVALID_ARG, "mjs_encoder_blend: " + why); };
+  if (!dst || !src) return refuse("an encoder is null");
+  if (dst->desc.device != src->desc.device) return refuse("the encoders live on different devices");
+  if (dst->desc.height != src->desc.height || dst->desc.width != src->desc.width || dst->desc.features_dim != src->desc.features_dim)
+    return refuse("the encoders differ in shape");
+  if (!src->loaded) return refuse("the source encoder has no parameters yet (mjs_encoder_load)");
+  if (!(tau > 0.0 && tau <= 1.0)) return refuse("tau must lie in (0, 1]");
+  if (tau != 1.0 && !dst->loaded) return refuse("tau != 1 into an encoder that has no parameters yet (tau == 1 copies)");
+  if (dst == src) return MJS_OK;  // a blend of a copy with itself
+  DeviceGuard dev_(dst->desc.device);
+  HIP_TRY(nullptr, dev_.err);
+  crit::BlendParams p{};
+  p.L = encoder_layout_of(dst);
+  p.dst[0] = encoder_packed_of(dst);
+  p.src[0] = encoder_packed_of(src);
+  const dim3 grid((unsigned)((p.L.off[8] + 255) / 256), 1);
+  if (tau == 1.0) crit::blend_kernel<true><<<grid, 256, 0, (hipStream_t)stream>>>(p, 0.0f, 1.0f);
+  else crit::blend_kernel<false><<<grid, 256, 0, (hipStream_t)stream>>>(p, (float)(1.0 - tau), (float)tau);
+  HIP_TRY(nullptr, hipGetLastError());
+  dst->loaded = true;
+  return MJS_OK;
+}
+
+int mjs_encoder_export(const mjs_encoder* e, const mjs_encoder_weights* out, void* stream) {
+  const auto refuse = [](const std::string& why) { return fail(nullptr, MJS_ERR_INVALID_ARG, "mjs_encoder_export: " + why); };
+  if (!e || !out) return refuse("null argument");
+  if (out->struct_size != sizeof(mjs_encoder_weights)) return refuse("mjs_encoder_weights.struct_size does not match this library's header");
+  if (!e->loaded) return refuse("the encoder has no parameters yet (mjs_encoder_load)");
+  if (!encoder_tensors_given(out)) return refuse("a weight or bias pointer is null");
+  DeviceGuard dev_(e->desc.device);
+  HIP_TRY(nullptr, dev_.err);
+  const crit::Packed P = encoder_packed_of(e);
+  launch_encoder_unpack(e, P.seg, out, (hipStream_t)stream);
   HIP_TRY(nullptr, hipGetLastError());
   return MJS_OK;
 }

@@ -74,7 +74,9 @@ class DeviceEncoder(_NativeObject):
     one image size (csrc/mjs_encoder.h): uint8 [n, H, W, 3] frames, as :meth:`HipVectorEnv.render` writes them, to float32 features
     [n, F]. float32 with float32 accumulation; the division by 255 and the NHWC -> CHW reading are part of the kernel.
 
-    Like :class:`DeviceActor` it keeps references to the torch modules and :meth:`load` packs their CURRENT parameters."""
+    Like :class:`DeviceActor` it keeps references to the torch modules and :meth:`load` packs their CURRENT parameters. Once a
+    :class:`DeviceEncoderOptimizer` exists the packed copy is the master copy: :meth:`load` would overwrite the trained parameters
+    with the stale modules, :meth:`export` writes them back into torch, :meth:`blend_from` follows another encoder's copy."""
     _handle, _destroy = "_e", "mjs_encoder_destroy"
 
     def __init__(self, venv, conv1, conv2, conv3, fc, height, width):
@@ -186,6 +188,187 @@ class DeviceEncoder(_NativeObject):
             stream = torch.cuda.current_stream(self.device).cuda_stream
             nat.check(self._lib.mjs_encoder_features(self._e, images.data_ptr(), n, self.workspace(n).data_ptr(), out.data_ptr(), C.c_void_p(stream)))
         return out
+
+    def _weights_struct(self, tensors):
+        """mjs_encoder_weights over the flat list (weight, bias) of conv1, conv2, conv3, fc."""
+        return nat.MjsEncoderWeights(**{f: t.data_ptr() for f, t in zip(("conv1_w", "conv1_b", "conv2_w", "conv2_b", "conv3_w", "conv3_b", "fc_w", "fc_b"), tensors)})
+
+    def _empty_like_parameters(self):
+        """Fresh contiguous float32 tensors in torch layout: the flat list (weight, bias) of conv1, conv2, conv3, fc."""
+        out = []
+        for cin, cout, k, _ in _NATURE_CNN:
+            out += [torch.empty(cout, cin, k, k, dtype=torch.float32, device=self.device), torch.empty(cout, dtype=torch.float32, device=self.device)]
+        return out + [torch.empty(self.features_dim, self.flat_dim, dtype=torch.float32, device=self.device),
+                      torch.empty(self.features_dim, dtype=torch.float32, device=self.device)]
+
+    def _check_export_modules(self, modules):
+        """(conv1, conv2, conv3, fc) with this encoder's shapes, float32 on its device; ValueError otherwise."""
+        try:
+            conv1, conv2, conv3, fc = modules
+        except (TypeError, ValueError):
+            raise ValueError("modules must be (conv1, conv2, conv3, fc), as DeviceEncoder takes them") from None
+        for name, m, (cin, cout, k, _) in zip(("conv1", "conv2", "conv3"), (conv1, conv2, conv3), _NATURE_CNN):
+            if not _is_conv(m):
+                raise ValueError(f"{name}: {type(m).__name__} is not a Conv2d")
+            _check_parameters(name, m, "Conv2d", "encoder", self.device)
+            if tuple(m.weight.shape) != (cout, cin, k, k) or tuple(m.bias.shape) != (cout,):
+                raise ValueError(f"{name}: weight {tuple(m.weight.shape)} / bias {tuple(m.bias.shape)}, expected {(cout, cin, k, k)} / {(cout,)}")
+        if not _is_linear(fc):
+            raise ValueError(f"fc: {type(fc).__name__} is not a Linear layer (weight, bias, in_features, out_features)")
+        _check_parameters("fc", fc, "Linear", "encoder", self.device)
+        if tuple(fc.weight.shape) != (self.features_dim, self.flat_dim) or tuple(fc.bias.shape) != (self.features_dim,):
+            raise ValueError(f"fc: weight {tuple(fc.weight.shape)} / bias {tuple(fc.bias.shape)}, expected {(self.features_dim, self.flat_dim)} / {(self.features_dim,)}")
+        return conv1, conv2, conv3, fc
+
+    def export(self, modules=None):
+        """The packed parameters into ``modules = (conv1, conv2, conv3, fc)`` (default: the modules this object was made from), with
+        ``copy_`` under ``no_grad``: the way back into torch after steps of a :class:`DeviceEncoderOptimizer`. Small kernels on the
+        current stream, no synchronisation. Returns ``(conv1, conv2, conv3, fc)``."""
+        mods = self._check_export_modules((*self.convs, self.fc) if modules is None else modules)
+        if self._e is None:
+            raise nat.MjsError("the encoder is closed")
+        staged = self._empty_like_parameters()
+        w = self._weights_struct(staged)
+        launch = self._lib.mjs_encoder_export
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        nat.check(launch(self._e, C.byref(w), C.c_void_p(stream)))
+        with torch.no_grad():
+            for k, m in enumerate(mods):
+                m.weight.copy_(staged[2 * k])
+                m.bias.copy_(staged[2 * k + 1])
+        return mods
+
+    def blend_from(self, other, tau):
+        """``packed = (1 - tau) * packed + tau * other's packed`` (SB3's ``polyak_update`` between two packed copies, one launch): what
+        a target critic's own extractor does after every step of the online one. ``other``: a :class:`DeviceEncoder` of the same
+        image size and ``features_dim`` on the same device; ``tau`` in (0, 1], ``tau = 1`` copies."""
+        if not isinstance(other, DeviceEncoder):
+            raise ValueError(f"other must be a DeviceEncoder, got {type(other).__name__}")
+        tau = float(tau)
+        if not 0.0 < tau <= 1.0:
+            raise ValueError(f"tau must lie in (0, 1], got {tau}")
+        if other.device != self.device:
+            raise ValueError(f"the other encoder lives on {other.device}, this one on {self.device}")
+        mine, theirs = (self.height, self.width, self.features_dim), (other.height, other.width, other.features_dim)
+        if mine != theirs:
+            raise ValueError(f"the encoders differ in shape: (height, width, features_dim) {mine} against {theirs}")
+        if self._e is None or other._e is None:
+            raise nat.MjsError("the encoder is closed")
+        blend = self._lib.mjs_encoder_blend
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        nat.check(blend(self._e, other._e, tau, C.c_void_p(stream)))
+
+
+class DeviceEncoderOptimizer(_NativeObject):
+    """The backward pass of a :class:`DeviceEncoder` and ``torch.optim.Adam`` on its packed parameters (csrc/mjs_encoder_train.h)::
+
+        features = cnn(images); features.backward(dfeatures); optimizer.step()              # torch.optim.Adam, SB3's defaults
+
+    ``dfeatures`` is read as it is (the ``1/B`` of a mean loss is the caller's, as with autograd). With a head of any kind in torch -
+    ``f = enc.features(images).requires_grad_(); loss(head(f)).backward(); opt.step(images, f.grad)`` - the CNN trains on the device.
+    The sums over the batch are bitwise reproducible. The packed copy is the master copy from the first step on:
+    ``encoder.features`` and the visual rollout see every step at once, a target encoder follows with
+    ``target.blend_from(encoder, tau)``, ``encoder.export()`` refreshes the torch modules, and ``encoder.load()`` would overwrite the
+    trained parameters with the stale modules. The optimiser keeps the encoder alive."""
+    _handle, _destroy = "_o", "mjs_encoder_opt_destroy"
+
+    def __init__(self, encoder, lr=3e-4, betas=(0.9, 0.999), eps=1e-8):
+        self._o = None
+        if not isinstance(encoder, DeviceEncoder):
+            raise ValueError(f"encoder must be a DeviceEncoder, got {type(encoder).__name__}")
+        self.lr = DeviceCriticOptimizer._checked_lr(lr)
+        try:
+            beta1, beta2 = (float(b) for b in betas)
+        except (TypeError, ValueError):
+            raise ValueError("betas must be two floats in [0, 1)") from None
+        if not (0.0 <= beta1 < 1.0 and 0.0 <= beta2 < 1.0):
+            raise ValueError(f"betas must lie in [0, 1), got {(beta1, beta2)}")
+        eps = float(eps)
+        if not 0.0 < eps < float("inf"):
+            raise ValueError(f"eps must be positive and finite, got {eps}")
+        self.betas, self.eps = (beta1, beta2), eps
+        self.encoder, self.device = encoder, encoder.device
+        self.step_count = 0
+        self._workspace = None
+        if encoder._e is None:
+            raise nat.MjsError("the encoder is closed")
+        # ---- native from here on
+        self._lib = encoder._lib
+        desc = nat.MjsEncoderOptDesc(lr=self.lr, beta1=beta1, beta2=beta2, eps=eps)
+        o = C.c_void_p()
+        nat.check(self._lib.mjs_encoder_opt_create(encoder._e, C.byref(desc), C.byref(o)))
+        self._o = o
+
+    def _checked(self, images, dfeatures):
+        """n, with both tensors checked; ValueError before anything native."""
+        e = self.encoder
+        if not isinstance(images, torch.Tensor) or images.dim() != 4:
+            raise ValueError(f"images must be a contiguous uint8 tensor [n, {e.height}, {e.width}, 3] on {self.device}")
+        n = int(images.shape[0])
+        if tuple(images.shape) != (n, e.height, e.width, 3) or images.dtype != torch.uint8 or images.device != self.device or not images.is_contiguous():
+            raise ValueError(f"images must be a contiguous uint8 tensor [n, {e.height}, {e.width}, 3] on {self.device}")
+        if (not isinstance(dfeatures, torch.Tensor) or tuple(dfeatures.shape) != (n, e.features_dim) or dfeatures.dtype != torch.float32
+                or dfeatures.device != self.device or not dfeatures.is_contiguous()):
+            raise ValueError(f"dfeatures must be a contiguous float32 tensor [{n}, {e.features_dim}] on {self.device}")
+        return n
+
+    def _open(self):
+        if self.encoder._e is None:
+            raise nat.MjsError("the encoder is closed")
+        if self._o is None:
+            raise nat.MjsError("the optimiser is closed")
+
+    def workspace(self, n):
+        """A float32 device tensor of mjs_encoder_train_workspace_bytes(n) (kept and reused while it is large enough)."""
+        floats = int(self._lib.mjs_encoder_train_workspace_bytes(self.encoder._e, int(n))) // 4
+        if self._workspace is None or self._workspace.numel() < floats:
+            self._workspace = torch.empty(floats, dtype=torch.float32, device=self.device)
+        return self._workspace
+
+    def _args(self, images, dfeatures, n, features=None, grads=None, activations=None):
+        acts = (C.c_void_p * 3)(*[t.data_ptr() for t in activations]) if activations is not None else (C.c_void_p * 3)()
+        return nat.MjsEncoderGradArgs(n=n, rgb_dev=images.data_ptr(), dfeatures_dev=dfeatures.data_ptr(), workspace_dev=self.workspace(n).data_ptr(),
+                                      features_out_dev=features.data_ptr() if features is not None else None,
+                                      grads_out=C.pointer(grads) if grads is not None else None, activations_out_dev=acts)
+
+    def step(self, images, dfeatures, lr=None, return_parts=False):
+        """One Adam step on the gradient of ``sum(features * dfeatures)`` with the learning rate ``lr`` (default: the constructor's).
+        Nine launches on the current stream; nothing is read back. Returns ``None``, or with ``return_parts`` a dict with ``features``
+        [n, F] (BEFORE the step). An empty batch does nothing and is not counted."""
+        n = self._checked(images, dfeatures)
+        lr = self.lr if lr is None else DeviceCriticOptimizer._checked_lr(lr)
+        self._open()
+        features = torch.empty(n, self.encoder.features_dim, dtype=torch.float32, device=self.device) if return_parts else None
+        if n:
+            args = self._args(images, dfeatures, n, features)
+            update = self._lib.mjs_encoder_update
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            nat.check(update(self._o, C.byref(args), lr, C.c_void_p(stream)))
+            self.step_count += 1
+        return {"features": features} if return_parts else None
+
+    def gradients(self, images, dfeatures):
+        """The gradients :meth:`step` would apply, and no update: a dict with ``features`` [n, F], ``grads`` (a list of ``(weight_grad,
+        bias_grad)`` in torch layout for conv1, conv2, conv3, fc) and ``activations`` (``conv1`` [n, P1, 32], ``conv2`` [n, P2, 64],
+        ``flat`` [n, flat_dim], post-ReLU: the masks the backward pass used)."""
+        n = self._checked(images, dfeatures)
+        self._open()
+        e = self.encoder
+        h1, w1 = (e.height - 8) // 4 + 1, (e.width - 8) // 4 + 1
+        h2, w2 = (h1 - 4) // 2 + 1, (w1 - 4) // 2 + 1
+        new = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=self.device)  # noqa: E731
+        features = new(n, e.features_dim)
+        acts = {"conv1": new(n, h1 * w1, 32), "conv2": new(n, h2 * w2, 64), "flat": new(n, e.flat_dim)}
+        flat = e._empty_like_parameters()
+        if n:
+            args = self._args(images, dfeatures, n, features, e._weights_struct(flat), (acts["conv1"], acts["conv2"], acts["flat"]))
+            grad = self._lib.mjs_encoder_grad
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            nat.check(grad(e._e, self._o, C.byref(args), C.c_void_p(stream)))
+        else:
+            for t in flat:
+                t.zero_()
+        return {"features": features, "grads": [(flat[2 * k], flat[2 * k + 1]) for k in range(4)], "activations": acts}
 
 
 class DeviceActor(_NativeObject):
