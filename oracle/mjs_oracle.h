@@ -215,6 +215,9 @@ int om_obs_dim_for(const om_task_config* cfg); /* Planar-Push: 5 + 2 * block slo
 int om_action_dim(int task);
 void om_env_init(om_env* e, const om_task_config* cfg, uint32_t seed);
 void om_env_seed(om_env* e, uint32_t seed);
+/* the env's stream in the form of numpy's RandomState.get_state(): key words and cursor (0..624; 624 = regenerate before the next word) */
+void om_env_get_rng(const om_env* e, uint32_t mt[624], int* pos);
+void om_env_set_rng(om_env* e, const uint32_t mt[624], int pos);
 void om_env_reset(om_env* e, om_step_out* out);
 void om_env_step(om_env* e, const double* action, om_step_out* out);
 
@@ -279,6 +282,7 @@ om_batch* om_batch_create(const om_task_config* cfg, int n, uint32_t base_seed);
 void om_batch_destroy(om_batch* b);
 om_env* om_batch_env(om_batch* b, int i);
 void om_batch_reset(om_batch* b, om_step_out* outs);
+void om_batch_reset_mt(om_batch* b, om_step_out* outs, int nthreads); /* om_batch_reset over threads */
 void om_batch_step(om_batch* b, const double* actions /*[n,A]*/, om_step_out* outs, int nthreads);
 int om_sizeof_step_out(void);
 

@@ -428,6 +428,16 @@ int om_sizeof_step_out(void) { return (int)sizeof(om_step_out); }
 
 void om_env_seed(om_env* e, uint32_t seed) { om_rng_seed(&e->rng, seed); }
 
+/* the env's stream as numpy's RandomState.get_state() gives it: the 624 key words and the cursor (0..624; 624 = regenerate first) */
+void om_env_get_rng(const om_env* e, uint32_t mt[624], int* pos) {
+  memcpy(mt, e->rng.mt, sizeof e->rng.mt);
+  *pos = e->rng.pos;
+}
+void om_env_set_rng(om_env* e, const uint32_t mt[624], int pos) {
+  memcpy(e->rng.mt, mt, sizeof e->rng.mt);
+  e->rng.pos = pos;
+}
+
 void om_env_init(om_env* e, const om_task_config* cfg, uint32_t seed) {
   memset(e, 0, sizeof *e);
   e->cfg = *cfg;
@@ -887,6 +897,11 @@ om_batch* om_batch_create(const om_task_config* cfg, int n, uint32_t base_seed) 
 void om_batch_destroy(om_batch* b) { free(b->envs); free(b); }
 om_env* om_batch_env(om_batch* b, int i) { return &b->envs[i]; }
 void om_batch_reset(om_batch* b, om_step_out* outs) {
+  for (int i = 0; i < b->n; i++) om_env_reset(&b->envs[i], &outs[i]);
+}
+/* the same resets, the envs spread over threads (they share nothing; Planar-Push runs 150 settle steps in each) */
+void om_batch_reset_mt(om_batch* b, om_step_out* outs, int nthreads) {
+#pragma omp parallel for num_threads(nthreads) schedule(dynamic)
   for (int i = 0; i < b->n; i++) om_env_reset(&b->envs[i], &outs[i]);
 }
 void om_batch_step(om_batch* b, const double* actions, om_step_out* outs, int nthreads) {

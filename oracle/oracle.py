@@ -93,6 +93,7 @@ def lib() -> C.CDLL:
         L.om_batch_env.argtypes = [C.c_void_p, C.c_int]
         L.om_batch_env.restype = C.c_void_p
         L.om_batch_reset.argtypes = [C.c_void_p, C.c_void_p]
+        L.om_batch_reset_mt.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.om_batch_step.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         L.om_env_seed.argtypes = [C.c_void_p, C.c_uint32]
         L.om_render_pointmass.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
@@ -229,6 +230,30 @@ class OracleBatch:
         for i in range(self.n):
             lib().om_env_seed(lib().om_batch_env(self._h, i), (base_seed + i) & 0xFFFFFFFF)
 
+    def rng_state(self):
+        """(mt uint32 [624, N], pos int32 [N]): every env's stream, laid out as HipVectorEnv.get_rng_state gives it; column i and
+        pos[i] are what np.random.RandomState.get_state() calls the key and pos."""
+        L = lib()
+        L.om_env_get_rng.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.om_env_get_rng.restype = None
+        mt, pos = np.zeros((self.n, 624), np.uint32), np.zeros(self.n, np.int32)
+        for i in range(self.n):
+            L.om_env_get_rng(L.om_batch_env(self._h, i), mt[i].ctypes.data, pos[i:].ctypes.data)
+        return np.ascontiguousarray(mt.T), pos
+
+    def set_rng_state(self, rng_state):
+        """load (mt [624, N], pos [N]) as rng_state returns it; a cursor lies in 0..624, as numpy's set_state demands"""
+        L = lib()
+        L.om_env_set_rng.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.om_env_set_rng.restype = None
+        mt, pos = rng_state
+        mt = np.ascontiguousarray(np.asarray(mt, dtype=np.uint32).T)
+        pos = np.asarray(pos, dtype=np.int64)
+        assert mt.shape == (self.n, 624) and pos.shape == (self.n,)
+        assert ((pos >= 0) & (pos <= 624)).all(), "cursor outside 0..624"
+        for i in range(self.n):
+            L.om_env_set_rng(L.om_batch_env(self._h, i), mt[i].ctypes.data, int(pos[i]))
+
     def _result(self):
         o = self._out
         return {
@@ -246,7 +271,10 @@ class OracleBatch:
         }
 
     def reset(self):
-        lib().om_batch_reset(self._h, self._out.ctypes.data)
+        if self.nthreads > 1:  # the envs share nothing: the same results, sooner (Planar-Push settles 150 steps per reset)
+            lib().om_batch_reset_mt(self._h, self._out.ctypes.data, self.nthreads)
+        else:
+            lib().om_batch_reset(self._h, self._out.ctypes.data)
         return self._result()
 
     def reset_envs(self, indices):

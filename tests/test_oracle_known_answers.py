@@ -29,6 +29,30 @@ def test_rng_matches_numpy_randomstate(oracle_mod, seed):
     assert ours == ref
 
 
+@pytest.mark.parametrize("pos", [0, 1, 311, 621, 622, 623, 624])
+def test_env_stream_loads_numpy_state_at_any_cursor(oracle_mod, pos):
+    # a state as numpy hands it out, with the cursor moved: 621..623 put the regeneration inside the reset's eight words (an odd
+    # cursor between the two words of one uniform); the env continues as numpy does and reports the state numpy reports
+    n = 3
+    rss = [np.random.RandomState(77 + i) for i in range(n)]
+    for i, rs in enumerate(rss):
+        rs.uniform(size=40 + i)
+        rs.set_state(("MT19937", rs.get_state()[1], pos))
+    b = oracle_mod.OracleBatch(oracle_mod.TASK_POINTMASS, n, 5)
+    key = np.stack([rs.get_state()[1] for rs in rss], axis=1)
+    b.set_rng_state((key, np.full(n, pos, np.int32)))
+    mt, p = b.rng_state()
+    assert mt.dtype == np.uint32 and mt.shape == (624, n) and p.dtype == np.int32 and p.shape == (n,)
+    assert np.array_equal(mt, key) and np.array_equal(p, np.full(n, pos))
+    obs = b.reset()["obs"]
+    mt, p = b.rng_state()
+    for i, rs in enumerate(rss):
+        gx, gy, px, py = (rs.uniform(-0.45, 0.45) for _ in range(4))
+        assert np.array_equal(obs[i].view(np.uint64), np.array([px, py, gx, gy]).view(np.uint64)), (i, pos)
+        _, k, q = rs.get_state()[:3]
+        assert np.array_equal(mt[:, i], k) and p[i] == q, (i, pos)
+
+
 def test_reset_draws_known_answers(oracle_mod):
     # SURVEY.md App. A.6 (computed there with numpy only): goal_x, goal_y, point_x, point_y
     expect = {
